@@ -21,7 +21,7 @@ ROOT = Path(__file__).resolve().parents[1]
 def test_c5_two_ranks_parity():
     env = dict(os.environ, ORBSLAM_DIST_BACKEND="gloo", PYTHONUNBUFFERED="1")
     env = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--launch-timeout", "220",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--launch-timeout", "220", "--full",
            "--steps", "3", "--warmup", "1", "--check-parity", "--no-cpu-baseline", "--no-latency",
            "--no-e2e", "--no-rgbd", "--no-track", "--no-pose", "--no-bow", "--no-bowmatch", "--no-newpts",
            "--no-isolated", "--no-alt-resize", "--lba-steps", "2"]
@@ -66,7 +66,7 @@ def test_rccl_single_rank():
     env = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--check-parity", "--no-cpu-baseline", "--no-latency",
+           "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--check-parity", "--no-cpu-baseline", "--no-latency",
            "--no-e2e", "--no-rgbd", "--no-track", "--no-pose", "--no-bow", "--no-bowmatch", "--no-newpts",
            "--no-isolated", "--no-alt-resize", "--lba-steps", "2"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

@@ -5,8 +5,9 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$R"; mkdir -p gpurun_out
 timeout -k 10 300 python -u -m pytest tests/test_stereo_gpu.py tests/test_matcher_gpu.py tests/test_host_cpp_gpu.py -m gpu -x -q --timeout 200 --timeout-method thread -p no:cacheprovider > gpurun_out/r02a_tests.log 2>&1
 rc=$?; tail -3 gpurun_out/r02a_tests.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py --no-cpu-baseline --no-lba --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts > gpurun_out/r02a_bench.json 2> gpurun_out/r02a_bench.err
-rc=$?; cat gpurun_out/r02a_bench.json; tail -3 gpurun_out/r02a_bench.err; [ $rc -eq 0 ] || exit $rc
+B=$(mktemp -d)   # the bench line and its stderr
+timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-lba --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts > "$B/r02a_bench.json" 2> "$B/r02a_bench.err"
+rc=$?; cat "$B/r02a_bench.json"; tail -3 "$B/r02a_bench.err"; [ $rc -eq 0 ] || exit $rc
 python -c "
 import numpy as np, sys
 sys.path.insert(0,'orb-slam2-noted_amd/python')

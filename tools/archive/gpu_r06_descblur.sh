@@ -7,7 +7,7 @@ set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; O="$R/gpurun_out"; mkdir -p "$O"; cd "$R"
 V=orb-slam2-noted_amd/build/var_descblur/liborbslam2_amd.so
 B=orb-slam2-noted_amd/build/var_base/liborbslam2_amd.so
-timeout -k 10 300 python bench.py --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency \
+timeout -k 10 300 python bench.py --full --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency \
   --no-cpu-baseline --steps 5 > "$O/r06_lba_windows.json" 2> "$O/r06_lba_windows.err"
 rc=$?; echo "lba windows rc=$rc"; [ $rc -eq 0 ] || exit $rc
 ORBSLAM_AMD_LIB=$(realpath $V) timeout -k 10 600 python -u -m pytest tests/test_extract_gpu.py tests/test_stereo_gpu.py \

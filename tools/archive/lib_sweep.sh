@@ -3,7 +3,7 @@
 # VARIANTS="th16 th24" ARGSETS="--engines 3|--engines 1 --batch 256"
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$R"; mkdir -p gpurun_out
-BASE="--no-cpu-baseline --no-lba --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency"
+BASE="--full --no-cpu-baseline --no-lba --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency"
 IFS='|' read -ra SETS <<< "${ARGSETS:---engines 3}"
 IFS='|' read -ra ENVS <<< "${ENVSETS:-NONE=0}"
 for ev in "${ENVS[@]}"; do

@@ -8,7 +8,7 @@ NEW="$R/orb-slam2-noted_amd/liborbslam2_amd.so"
 cd "$R"
 timeout -k 10 600 python -u -m pytest tests/test_lba_gpu.py tests/test_host_cpp_gpu.py tests/test_c5_rehearsal_gpu.py -x -q --timeout 300 --timeout-method thread > "$OUT/ab_lba_tests.log" 2>&1
 rc=$?; tail -2 "$OUT/ab_lba_tests.log"; [ $rc -eq 0 ] || exit $rc
-LEGS="--no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
+LEGS="--full --no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
 bash tools/ab_bench.sh "$BASE" "$NEW" 4 $LEGS > "$OUT/ab_lba.log" 2>&1 || exit $?
 python3 - "$OUT/ab_lba.log" <<'PY'
 import json, sys

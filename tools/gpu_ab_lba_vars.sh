@@ -5,7 +5,7 @@ set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; OUT="$R/gpurun_out"; mkdir -p "$OUT"
 cd "$R"
 PROD="$R/orb-slam2-noted_amd/liborbslam2_amd.so"
-LEGS="--no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
+LEGS="--full --no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
 for V in "$@"; do
   bash tools/ab_bench.sh "$PROD" "$V" 3 $LEGS >> "$OUT/ab_lba_vars.log" 2>&1 || exit $?
 done

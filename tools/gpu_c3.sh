@@ -3,7 +3,7 @@
 # and which HIP / HSA runtimes one bench process maps (torch's bundled vs /opt/rocm's).
 set -u
 R="$GRAFT_REPO_ROOT"; OUT="$R/gpurun_out"; mkdir -p "$OUT"
-ARGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --rgbd-steps 10"
+ARGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --rgbd-steps 10"
 cd "$R"
 timeout -k 10 120 python3 - > "$OUT/runtime_maps.txt" 2>&1 <<'PY'
 import sys; sys.path.insert(0, "orb-slam2-noted_amd/python")

@@ -2,7 +2,7 @@
 # C3 (RGB-D) batch size x engines sweep, same box:  tools/gpu_c3_batch.sh -> gpurun_out/c3_batch.log
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; OUT="$R/gpurun_out"; mkdir -p "$OUT"
-ARGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e --rgbd-steps 40"
+ARGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e --rgbd-steps 40"
 cd "$R"
 for rep in 1 2; do
   for cfg in "256 4" "512 4" "512 3" "512 2" "768 3" "1024 2"; do

@@ -2,7 +2,7 @@
 # C3 leg alone at 4, 5 and 6 engines (40 timed batches), alternating, 2 rounds -> gpurun_out/c3_engines.log
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; OUT="$R/gpurun_out"; mkdir -p "$OUT"; cd "$R"
-ARGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e --rgbd-steps 40"
+ARGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e --rgbd-steps 40"
 for rep in 1 2; do
   for e in 4 5 6; do
     line=$(timeout -k 10 180 python3 bench.py $ARGS --rgbd-engines $e 2>/dev/null | tail -1) || exit $?

@@ -3,7 +3,7 @@
 # and a variant ($1), plus one engine alone (--rgbd-engines 1) for each: per-kernel durations.
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; O="$R/gpurun_out"; mkdir -p "$O"
-ARGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
+ARGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
 cd /tmp && export TMPDIR=/tmp
 for tag in prod $1; do
   LIB="$R/orb-slam2-noted_amd/liborbslam2_amd.so"; [ "$tag" = prod ] || LIB="$R/orb-slam2-noted_amd/build/var_$tag/liborbslam2_amd.so"

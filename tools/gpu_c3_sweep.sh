@@ -4,7 +4,7 @@
 #   tools/gpu_c3_sweep.sh  -> gpurun_out/c3_sweep.log, gpurun_out/c3prof/
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; OUT="$R/gpurun_out"; mkdir -p "$OUT"
-ARGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
+ARGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
 cd "$R"
 for rep in 1 2; do
   for cfg in "10 3" "40 3" "40 2" "40 4" "80 3"; do

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"
 V=$1
 O=$R/gpurun_out; mkdir -p "$O"
 MB=$R/tools/microbench
-LEGS="--no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency"
+LEGS="--full --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency"
 timeout -k 10 120 "$MB/fetch_calib" > "$O/fc1_bytes.json" &&
 timeout -k 10 120 "$MB/fetch_calib2" > "$O/fc2_bytes.json" &&
 bash "$R/tools/pmc_reqsize.sh" fc1 "$MB/fetch_calib" &&

@@ -17,13 +17,13 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/r05_smoke.log" 2>&1
       rc=$?; echo "smoke rc=$rc"; tail -1 "$O/r05_smoke.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > "$O/r05_bench.json" 2> "$O/r05_bench.err"
+      timeout -k 10 600 python bench.py --full > "$O/r05_bench.json" 2> "$O/r05_bench.err"
       rc=$?; echo "bench rc=$rc"; head -c 1500 "$O/r05_bench.json"; echo; [ $rc -eq 0 ] || exit $rc ;;
     abdesc)
       timeout -k 10 900 python tools/ab_c2.py "$R/orb-slam2-noted_amd/liborbslam2_amd.so" "$V/var_noclip/liborbslam2_amd.so" 4 > "$O/r05_ab_desc_clip.log" 2>&1
       rc=$?; echo "abdesc rc=$rc"; grep SUMMARY "$O/r05_ab_desc_clip.log"; [ $rc -eq 0 ] || exit $rc ;;
     ablba)
-      LEGS="--no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
+      LEGS="--full --no-c2 --no-cpu-baseline --no-profile --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency --steps 1 --warmup 1 --lba-steps 40"
       timeout -k 10 600 bash tools/ab_bench.sh "$V/var_solve16/liborbslam2_amd.so" "$R/orb-slam2-noted_amd/liborbslam2_amd.so" 4 $LEGS > "$O/r05_ab_lba_solve.log" 2>&1
       rc=$?; echo "ablba rc=$rc"; [ $rc -eq 0 ] || exit $rc
       python3 - "$O/r05_ab_lba_solve.log" <<'PY'

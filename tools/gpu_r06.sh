@@ -4,6 +4,7 @@
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; O="$R/gpurun_out"; mkdir -p "$O"; cd "$R"
 TAG="${TAG:-r06}"
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the bench step runs every leg, not the headline alone
 for s in ${STEPS:-tests smoke bench}; do
   case $s in
     tests)

@@ -13,7 +13,7 @@ if [ "${C2:-1}" = 1 ]; then
   timeout -k 10 900 python tools/ab_c2.py "$BASE" orb-slam2-noted_amd/liborbslam2_amd.so ${ROUNDS:-4} > "$O/${TAG}_c2.log" 2>&1
   rc=$?; echo "c2 ab rc=$rc"; grep SUMMARY "$O/${TAG}_c2.log"; [ $rc -eq 0 ] || exit $rc
 fi
-LEGS="--no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
+LEGS="--full --no-c2 --no-lba --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-latency --no-cpu-baseline --no-profile --no-e2e"
 bash tools/ab_bench.sh "$BASE" orb-slam2-noted_amd/liborbslam2_amd.so ${ROUNDS:-4} $LEGS > "$O/${TAG}_c3.log" 2>&1
 rc=$?; echo "c3 ab rc=$rc"
 python3 - "$O/${TAG}_c3.log" <<'PY'

@@ -7,7 +7,7 @@ TAG="${TAG:-r06_lba}"
 timeout -k 10 600 python -u -m pytest tests/test_lba_gpu.py -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider \
   > "$O/${TAG}_tests.log" 2>&1
 rc=$?; echo "lba tests rc=$rc"; tail -4 "$O/${TAG}_tests.log"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency \
+timeout -k 10 300 python bench.py --full --no-rgbd --no-track --no-pose --no-bow --no-bowmatch --no-newpts --no-e2e --no-latency \
   --no-cpu-baseline --steps 5 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 echo done

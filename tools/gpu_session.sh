@@ -10,6 +10,7 @@ stop_if_fatal() {  # $1 = rc, $2 = step; pytest rc 1 (= test failures) is not fa
   if [ "$rc" -ne 0 ] && [ "$rc" -ne 1 ]; then echo "FATAL rc=$rc in $2" | tee -a $OUT/session.log; exit $rc; fi
 }
 STEPS="${STEPS:-tests smoke bench prof}"
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the bench and prof steps run every leg, not the headline alone
 for s in $STEPS; do
   case $s in
     tests)
