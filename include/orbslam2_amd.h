@@ -602,6 +602,62 @@ int orbn_stage(orbn_engine *e, int slot, const orbn_keyframe *kf1, const orbn_ke
 int orbn_run_batch(orbn_engine *e, int n_slots, void *stream);
 int orbn_fetch(orbn_engine *e, int slot, float *x3d, uint8_t *ok, int32_t *nnew);
 
+/* -------- Sim3 RANSAC (replaces Sim3Solver in LoopClosing::ComputeSim3) -------- */
+
+#define ORBS_MAX_HYP 300   /* LoopClosing's SetRansacParameters(0.99, 20, 300) (LoopClosing.cc:365) */
+
+/* One Sim3Solver (include/Sim3Solver.h:40-170) after its constructor (Sim3Solver.cc:54-147), with
+ * the RANSAC samples of iterate() (:240-261) made an input: the reference draws them from glibc's
+ * process-global rand() (DUtils::Random::RandomInt, Thirdparty/DBoW2/DUtils/Random.cpp:47-50), a
+ * stream that cannot live on the device, so the caller draws n_hyp triplets up front. Host pointers.
+ * max_err1 / max_err2 are mvnMaxError1 / mvnMaxError2 as CheckInliers' comparison sees them: the
+ * members are std::vector<size_t> (Sim3Solver.h:163-164), so 9.210 * sigma2 is truncated to an
+ * integer when pushed (:117-118) and `err < mvnMaxError[i]` (:480) compares against that integer
+ * converted to float -- octave 1 (sigma2 = 1.44) tests against 13, not 13.26. The caller passes
+ * (float)(size_t)(9.210 * sigma2); this library keeps the truncation. */
+typedef struct {
+    int32_t n;                /* N: mvX3Dc1.size(), the compacted correspondences */
+    const float *X1c, *X2c;   /* [n][3] mvX3Dc1 / mvX3Dc2 (camera frames) */
+    const float *max_err1, *max_err2; /* [n] mvnMaxError1/2 as the comparison sees them */
+    float K1[4], K2[4];       /* fx fy cx cy of pKF1 / pKF2 */
+    int32_t fix_scale;        /* mbFixScale */
+    int32_t n_hyp;            /* 1..ORBS_MAX_HYP (300) */
+    const int32_t *triplets;  /* [n_hyp][3] indices into the correspondences, distinct */
+} orbs_problem;
+
+typedef struct {              /* caller-allocated */
+    int32_t *n_inliers;       /* [n_hyp] mnInliersi */
+    uint64_t *inlier_bits;    /* [n_hyp][(n+63)/64] mvbInliersi, bit i%64 of word i/64 */
+    float *R12, *t12, *s12;   /* [n_hyp][9] / [n_hyp][3] / [n_hyp] */
+} orbs_result;
+
+typedef struct orbs_engine orbs_engine;
+
+/* The engine is a host object until a call whose arguments passed every check needs the device:
+ * orbs_create / orbs_reserve succeed without a GPU, and every ORBX_EINVAL below is returned
+ * before the device is touched. */
+int orbs_create(orbs_engine **out);
+void orbs_destroy(orbs_engine *e);
+/* Hypothesis h of one solver: Sim3Solver::ComputeSim3 (Sim3Solver.cc:330-452) on the pairs
+ * triplets[3h..3h+2] -- Horn's closed form: float centroids, M = Pr2 * Pr1.t() and N, the eigenvector
+ * of N's largest eigenvalue (cv::eigen on CV_32F), ang = atan2(|vec|, q0) and cv::Rodrigues in
+ * double, the scale sum(Pr1 . P3) / sum(P3^2) in double or 1.0f under fix_scale, t = O1 - s R O2,
+ * T12 and T21 as :435-451 -- then CheckInliers (:458-488): both projections of every correspondence
+ * through Project (:515-539; float, invz = 1 / z with no sign test) against the FromCameraToImage
+ * points (:548-567), err1 < max_err1[i] && err2 < max_err2[i] (NaN / Inf: not an inlier). Outputs
+ * per hypothesis: mnInliersi, mvbInliersi as bits, mR12i, mt12i, ms12i. All hypotheses run in one
+ * launch; the early exit of iterate() (:270-288) is a scan over n_inliers the caller replays.
+ * ORBX_EINVAL: a NULL pointer, n < 3, n_hyp outside 1..ORBS_MAX_HYP, a triplet index outside
+ * [0, n) or repeated inside its triplet. */
+int orbs_evaluate(orbs_engine *e, const orbs_problem *p, orbs_result *r);
+/* Batched device-resident form (the candidates of one LoopClosing::ComputeSim3 call,
+ * LoopClosing.cc:363-404): stage each solver into a slot, one launch evaluates every hypothesis of
+ * every slot, fetch per slot. orbs_stage also returns ORBX_EINVAL for n > cap_n or n_hyp > cap_hyp. */
+int orbs_reserve(orbs_engine *e, int n_slots, int cap_n, int cap_hyp);
+int orbs_stage(orbs_engine *e, int slot, const orbs_problem *p);
+int orbs_run_batch(orbs_engine *e, int n_slots, void *stream);
+int orbs_fetch(orbs_engine *e, int slot, orbs_result *r);
+
 /* -------- local bundle adjustment (replaces Optimizer::LocalBundleAdjustment) -------- */
 
 /* The graph Optimizer::LocalBundleAdjustment (Optimizer.cc:646-898) builds from the map,

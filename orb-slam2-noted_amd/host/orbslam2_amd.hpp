@@ -12,11 +12,15 @@
 //                                                     ORBmatcher.h:102 (motion model)
 //   orbslam2_amd::ORBVocabulary                    <- DBoW2 TemplatedVocabulary<FORB>:
 //                                                     loadFromTextFile + transform (ComputeBoW)
+//   orbslam2_amd::Sim3Solver                        <- ORB_SLAM2::Sim3Solver (include/Sim3Solver.h:40-170)
 //
 // Error behaviour: the reference has no error path (it asserts / returns silently); a GPU
 // failure here throws std::runtime_error -- there is no CPU fallback.
 #pragma once
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -377,6 +381,268 @@ public:
               "orbn_triangulate");
         return nnew;
     }
+};
+
+
+// What Sim3Solver's constructor reads of a KeyFrame (Sim3Solver.cc:74-77, 111-112, 138-139).
+struct Sim3KeyFrame {
+    float Rcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // GetRotation(), row-major
+    float tcw[3] = {0, 0, 0};                     // GetTranslation()
+    float fx = 0, fy = 0, cx = 0, cy = 0;         // mK
+    std::vector<float> mvLevelSigma2;
+};
+
+// Entry i1 of vpMatched12 with everything the constructor dereferences (Sim3Solver.cc:84-135):
+// pMP1 = pKF1->GetMapPointMatches()[i1], pMP2 = vpMatched12[i1].
+struct Sim3Match {
+    bool pMP2 = false, pMP1 = false;      // the pointers are non-NULL
+    bool bad1 = false, bad2 = false;      // isBad()
+    int indexKF1 = -1, indexKF2 = -1;     // GetIndexInKeyFrame(pKF1 / pKF2)
+    int octave1 = 0, octave2 = 0;         // mvKeysUn[indexKF].octave
+    float Xw1[3] = {0, 0, 0}, Xw2[3] = {0, 0, 0};   // GetWorldPos()
+};
+
+// Sim3Solver with the reference's members over POD keyframe views. The RANSAC body runs on the GPU:
+// the first iterate() (or EvaluateAll over the candidates of one LoopClosing::ComputeSim3 call, one
+// launch for all) draws all mRansacMaxIts triplets and evaluates every hypothesis through orbs_*;
+// iterate() then replays the reference's loop (Sim3Solver.cc:234-297) over the stored counts, so
+// the round-robin of iterate(5) calls (LoopClosing.cc:378-404) costs no launch per call.
+// Deviation from the reference: for a given triplet sequence the results are the reference's, but
+// the random generator is consumed up front -- 3 * mRansacMaxIts draws per solver -- where the
+// reference stops drawing at the early exit, so the process-global rand() stream that later code
+// sees is advanced further. RandomInt is injectable (default: DUtils::Random::RandomInt over
+// rand(), Thirdparty/DBoW2/DUtils/Random.cpp:47-50) for deterministic runs.
+class Sim3Solver {
+public:
+    using RandomIntFn = std::function<int(int, int)>;
+
+    Sim3Solver(const Sim3KeyFrame &pKF1, const Sim3KeyFrame &pKF2, const std::vector<Sim3Match> &vpMatched12,
+               const bool bFixScale = true, RandomIntFn randomInt = RandomIntFn())
+        : mnIterations(0), mnBestInliers(0), mbFixScale(bFixScale), mRandomInt(randomInt ? randomInt : RandomIntFn(DefaultRandomInt)) {
+        mN1 = (int)vpMatched12.size();
+        mvnIndices1.reserve(mN1);
+        mvX3Dc1.reserve((size_t)mN1 * 3);
+        mvX3Dc2.reserve((size_t)mN1 * 3);
+        mvAllIndices.reserve(mN1);
+        size_t idx = 0;
+        for (int i1 = 0; i1 < mN1; i1++) {
+            const Sim3Match &m = vpMatched12[i1];
+            if (!m.pMP2) continue;
+            if (!m.pMP1) continue;
+            if (m.bad1 || m.bad2) continue;
+            if (m.indexKF1 < 0 || m.indexKF2 < 0) continue;
+            const float sigmaSquare1 = pKF1.mvLevelSigma2[m.octave1];
+            const float sigmaSquare2 = pKF2.mvLevelSigma2[m.octave2];
+            mvnMaxError1.push_back((size_t)(9.210 * sigmaSquare1));   // std::vector<size_t>: truncated (:117-118)
+            mvnMaxError2.push_back((size_t)(9.210 * sigmaSquare2));
+            mvnIndices1.push_back((size_t)i1);
+            ToCamera(pKF1, m.Xw1, mvX3Dc1);
+            ToCamera(pKF2, m.Xw2, mvX3Dc2);
+            mvAllIndices.push_back(idx);
+            idx++;
+        }
+        mK1[0] = pKF1.fx; mK1[1] = pKF1.fy; mK1[2] = pKF1.cx; mK1[3] = pKF1.cy;
+        mK2[0] = pKF2.fx; mK2[1] = pKF2.fy; mK2[2] = pKF2.cx; mK2[3] = pKF2.cy;
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability;
+        mRansacMinInliers = minInliers;
+        mRansacMaxIts = maxIterations;
+        N = (int)mvnIndices1.size();
+        float epsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N)
+            nIterations = 1;
+        else if (N < mRansacMinInliers)
+            nIterations = mRansacMaxIts;   // log of a negative number in the reference; iterate() returns at once
+        else
+            nIterations = (int)std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow(epsilon, 3)));
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mnIterations = 0;
+        mEvaluated = false;
+    }
+
+    // Evaluates every hypothesis of every solver in one launch (the candidates of one keyframe).
+    static void EvaluateAll(std::vector<Sim3Solver *> &vpSolvers) {
+        std::vector<Sim3Solver *> todo;
+        int capN = 3, capH = 1;
+        for (Sim3Solver *s : vpSolvers)
+            if (s && !s->mEvaluated && s->N >= s->mRansacMinInliers && s->N >= 3) {
+                s->DrawTriplets();
+                todo.push_back(s);
+                capN = std::max(capN, s->N);
+                capH = std::max(capH, s->mRansacMaxIts);
+            }
+        if (todo.empty()) return;
+        Engine &eng = engine();
+        check(orbs_reserve(eng.h, (int)todo.size(), capN, capH), "orbs_reserve");
+        for (size_t k = 0; k < todo.size(); k++) {
+            orbs_problem p = todo[k]->Problem();
+            check(orbs_stage(eng.h, (int)k, &p), "orbs_stage");
+        }
+        check(orbs_run_batch(eng.h, (int)todo.size(), nullptr), "orbs_run_batch");
+        for (size_t k = 0; k < todo.size(); k++) {
+            orbs_result r = todo[k]->Result();
+            check(orbs_fetch(eng.h, (int)k, &r), "orbs_fetch");
+            todo[k]->mEvaluated = true;
+        }
+    }
+
+    // Returns true where the reference returns a non-empty mBestT12 (T12 = [s R | t; 0 1], row-major).
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float T12[16] = nullptr) {
+        bNoMore = false;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers || N < 3) {   // N < 3: no min set can be drawn (the reference would index out of range)
+            bNoMore = true;
+            return false;
+        }
+        if (!mEvaluated) {
+            std::vector<Sim3Solver *> self{this};
+            EvaluateAll(self);
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            nCurrentIterations++;
+            const int h = mnIterations++;
+            const int mnInliersi = mvnInliers[h];
+            if (mnInliersi >= mnBestInliers) {
+                mnBestInliers = mnInliersi;
+                mnBest = h;
+                if (mnInliersi > mRansacMinInliers) {
+                    nInliers = mnInliersi;
+                    const size_t w = ((size_t)N + 63) / 64;
+                    for (int i = 0; i < N; i++)
+                        if ((mvInlierBits[(size_t)h * w + i / 64] >> (i % 64)) & 1) vbInliers[mvnIndices1[i]] = true;
+                    if (T12) {
+                        const float s = mvScale[h];
+                        for (int r = 0; r < 3; r++) {
+                            for (int c = 0; c < 3; c++) T12[4 * r + c] = s * mvRotation[(size_t)h * 9 + 3 * r + c];
+                            T12[4 * r + 3] = mvTranslation[(size_t)h * 3 + r];
+                        }
+                        T12[12] = T12[13] = T12[14] = 0;
+                        T12[15] = 1;
+                    }
+                    return true;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return false;
+    }
+
+    bool find(std::vector<bool> &vbInliers12, int &nInliers, float T12[16] = nullptr) {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers, T12);
+    }
+
+    // mBestRotation (row-major 3x3) / mBestTranslation / mBestScale; false before any iteration
+    bool GetEstimatedRotation(float R[9]) const {
+        if (mnBest < 0) return false;
+        for (int k = 0; k < 9; k++) R[k] = mvRotation[(size_t)mnBest * 9 + k];
+        return true;
+    }
+    bool GetEstimatedTranslation(float t[3]) const {
+        if (mnBest < 0) return false;
+        for (int k = 0; k < 3; k++) t[k] = mvTranslation[(size_t)mnBest * 3 + k];
+        return true;
+    }
+    float GetEstimatedScale() const { return mnBest < 0 ? 0.0f : mvScale[mnBest]; }
+
+    int GetNumCorrespondences() const { return N; }          // N
+    int GetMaxIterations() const { return mRansacMaxIts; }   // mRansacMaxIts after SetRansacParameters
+    int GetIterations() const { return mnIterations; }       // mnIterations
+    const std::vector<size_t> &GetMaxError1() const { return mvnMaxError1; }
+    const std::vector<int32_t> &GetTriplets() const { return mvTriplets; }
+
+    static int DefaultRandomInt(int min, int max) {   // DUtils::Random::RandomInt
+        int d = max - min + 1;
+        return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+    }
+
+private:
+    struct Engine {
+        orbs_engine *h = nullptr;
+        Engine() { check(orbs_create(&h), "orbs_create"); }
+        ~Engine() { orbs_destroy(h); }
+    };
+    static Engine &engine() {
+        static thread_local Engine eng;
+        return eng;
+    }
+
+    static void ToCamera(const Sim3KeyFrame &kf, const float Xw[3], std::vector<float> &out) {   // Rcw * X3Dw + tcw, float
+        for (int r = 0; r < 3; r++) {
+            float s = kf.Rcw[3 * r] * Xw[0];
+            s = s + kf.Rcw[3 * r + 1] * Xw[1];
+            s = s + kf.Rcw[3 * r + 2] * Xw[2];
+            out.push_back(s + kf.tcw[r]);
+        }
+    }
+
+    // the min sets of all mRansacMaxIts iterations, drawn as the reference's loop does (:240-261)
+    void DrawTriplets() {
+        mvTriplets.clear();
+        mvTriplets.reserve((size_t)mRansacMaxIts * 3);
+        std::vector<size_t> vAvailableIndices;
+        for (int it = 0; it < mRansacMaxIts; it++) {
+            vAvailableIndices = mvAllIndices;
+            for (short i = 0; i < 3; ++i) {
+                int randi = mRandomInt(0, (int)vAvailableIndices.size() - 1);
+                mvTriplets.push_back((int32_t)vAvailableIndices[randi]);
+                vAvailableIndices[randi] = vAvailableIndices.back();
+                vAvailableIndices.pop_back();
+            }
+        }
+    }
+
+    orbs_problem Problem() {
+        mvMaxErrorF1.resize(N);
+        mvMaxErrorF2.resize(N);
+        for (int i = 0; i < N; i++) {   // err < mvnMaxError[i]: the size_t converted to float (:480)
+            mvMaxErrorF1[i] = (float)mvnMaxError1[i];
+            mvMaxErrorF2[i] = (float)mvnMaxError2[i];
+        }
+        orbs_problem p{};
+        p.n = N;
+        p.X1c = mvX3Dc1.data();
+        p.X2c = mvX3Dc2.data();
+        p.max_err1 = mvMaxErrorF1.data();
+        p.max_err2 = mvMaxErrorF2.data();
+        for (int k = 0; k < 4; k++) {
+            p.K1[k] = mK1[k];
+            p.K2[k] = mK2[k];
+        }
+        p.fix_scale = mbFixScale ? 1 : 0;
+        p.n_hyp = mRansacMaxIts;
+        p.triplets = mvTriplets.data();
+        return p;
+    }
+
+    orbs_result Result() {
+        const size_t H = (size_t)mRansacMaxIts, w = ((size_t)N + 63) / 64;
+        mvnInliers.assign(H, 0);
+        mvInlierBits.assign(H * w, 0);
+        mvRotation.assign(H * 9, 0.0f);
+        mvTranslation.assign(H * 3, 0.0f);
+        mvScale.assign(H, 0.0f);
+        return orbs_result{mvnInliers.data(), mvInlierBits.data(), mvRotation.data(), mvTranslation.data(), mvScale.data()};
+    }
+
+    int mN1 = 0, N = 0;
+    std::vector<size_t> mvnIndices1, mvnMaxError1, mvnMaxError2, mvAllIndices;
+    std::vector<float> mvX3Dc1, mvX3Dc2, mvMaxErrorF1, mvMaxErrorF2;
+    float mK1[4], mK2[4];
+    int mnIterations, mnBestInliers, mnBest = -1;
+    bool mbFixScale, mEvaluated = false;
+    double mRansacProb = 0.99;
+    int mRansacMinInliers = 6, mRansacMaxIts = 300;
+    RandomIntFn mRandomInt;
+    std::vector<int32_t> mvTriplets, mvnInliers;
+    std::vector<uint64_t> mvInlierBits;
+    std::vector<float> mvRotation, mvTranslation, mvScale;
 };
 
 }  // namespace orbslam2_amd

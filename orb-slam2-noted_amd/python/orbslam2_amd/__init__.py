@@ -159,6 +159,13 @@ SIGNATURES = [
     ("orbn_stage", _I, [_P, _I, _P, _P, _P, _I, _F]),
     ("orbn_run_batch", _I, [_P, _I, _P]),
     ("orbn_fetch", _I, [_P, _I, _P, _P, _P]),
+    ("orbs_create", _I, [C.POINTER(C.c_void_p)]),
+    ("orbs_destroy", None, [_P]),
+    ("orbs_evaluate", _I, [_P, _P, _P]),
+    ("orbs_reserve", _I, [_P, _I, _I, _I]),
+    ("orbs_stage", _I, [_P, _I, _P]),
+    ("orbs_run_batch", _I, [_P, _I, _P]),
+    ("orbs_fetch", _I, [_P, _I, _P]),
 ]
 
 
@@ -1373,3 +1380,129 @@ class NewMapPoints:
         nnew = C.c_int32()
         _check(lib().orbn_fetch(self._h, slot, x3d.ctypes.data, ok.ctypes.data, C.byref(nnew)), "orbn_fetch")
         return nnew.value, x3d[:n_pairs], ok[:n_pairs]
+
+
+# ---- Sim3Solver (orbs_*): the RANSAC of LoopClosing::ComputeSim3 ------------------------------
+ORBS_MAX_HYP = 300
+
+
+class OrbsProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("max_err1", C.c_void_p),
+                ("max_err2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("fix_scale", C.c_int32),
+                ("n_hyp", C.c_int32), ("triplets", C.c_void_p)]
+
+
+class OrbsResult(C.Structure):
+    _fields_ = [("n_inliers", C.c_void_p), ("inlier_bits", C.c_void_p), ("R12", C.c_void_p), ("t12", C.c_void_p),
+                ("s12", C.c_void_p)]
+
+
+def orbs_problem(prob: dict):
+    """(OrbsProblem, arrays it points into) of a dict shaped like synth.sim3_solver_problem."""
+    keep = {k: np.ascontiguousarray(prob[k], np.float32) for k in ("X1c", "X2c", "max_err1", "max_err2")}
+    keep["triplets"] = np.ascontiguousarray(prob["triplets"], np.int32).reshape(-1, 3)
+    P = OrbsProblem()
+    P.n = len(keep["X1c"])
+    P.X1c, P.X2c, P.max_err1, P.max_err2 = (keep[k].ctypes.data for k in ("X1c", "X2c", "max_err1", "max_err2"))
+    P.K1[:] = [float(v) for v in np.asarray(prob["K1"], np.float32)]
+    P.K2[:] = [float(v) for v in np.asarray(prob["K2"], np.float32)]
+    P.fix_scale = 1 if prob["fix_scale"] else 0
+    P.n_hyp = len(keep["triplets"])
+    P.triplets = keep["triplets"].ctypes.data
+    return P, keep
+
+
+class Sim3Solver:
+    """Sim3Solver (include/Sim3Solver.h) on the GPU: every RANSAC hypothesis of a solver -- the
+    Horn solve of ComputeSim3 and the two-way reprojection test of CheckInliers -- in one launch,
+    then the early exit of iterate() replayed over the stored counts. Problems are dicts shaped like
+    synth.sim3_solver_problem: {"X1c", "X2c", "max_err1", "max_err2", "K1", "K2", "fix_scale",
+    "triplets"}; the triplets are an input because the reference's rand() stream is the host's."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        _check(lib().orbs_create(C.byref(h)), "orbs_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orbs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _result(n, n_hyp):
+        out = {"n_inliers": np.zeros(n_hyp, np.int32), "inlier_bits": np.zeros((n_hyp, (n + 63) // 64), np.uint64),
+               "R12": np.zeros((n_hyp, 3, 3), np.float32), "t12": np.zeros((n_hyp, 3), np.float32),
+               "s12": np.zeros(n_hyp, np.float32)}
+        R = OrbsResult(*(out[k].ctypes.data for k in ("n_inliers", "inlier_bits", "R12", "t12", "s12")))
+        return R, out
+
+    @staticmethod
+    def unpack_bits(bits: np.ndarray, n: int) -> np.ndarray:
+        """inlier_bits [n_hyp][(n+63)/64] -> mvbInliersi as bool [n_hyp][n]."""
+        b = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")
+        return b[:, :n].astype(bool)
+
+    def evaluate(self, prob: dict) -> dict:
+        P, keep = orbs_problem(prob)
+        R, out = self._result(P.n, P.n_hyp)
+        _check(lib().orbs_evaluate(self._h, C.byref(P), C.byref(R)), "orbs_evaluate")
+        return out
+
+    def reserve(self, n_slots: int, cap_n: int, cap_hyp: int = ORBS_MAX_HYP):
+        _check(lib().orbs_reserve(self._h, n_slots, cap_n, cap_hyp), "orbs_reserve")
+
+    def stage(self, slot: int, prob: dict):
+        P, keep = orbs_problem(prob)
+        _check(lib().orbs_stage(self._h, slot, C.byref(P)), "orbs_stage")
+
+    def run_batch(self, n_slots: int, stream=None):
+        _check(lib().orbs_run_batch(self._h, n_slots, stream), "orbs_run_batch")
+
+    def fetch(self, slot: int, n: int, n_hyp: int) -> dict:
+        R, out = self._result(n, n_hyp)
+        _check(lib().orbs_fetch(self._h, slot, C.byref(R)), "orbs_fetch")
+        return out
+
+    @staticmethod
+    def ransac_iterations(N: int, probability=0.99, min_inliers=20, max_iterations=300) -> int:
+        """mRansacMaxIts of SetRansacParameters (Sim3Solver.cc:156-194)."""
+        if N == min_inliers:
+            nit = 1
+        else:
+            eps = float(np.float32(min_inliers) / np.float32(max(N, 1)))
+            with np.errstate(all="ignore"):
+                v = np.ceil(np.log(1 - probability) / np.log(1 - eps ** 3))
+            nit = int(v) if np.isfinite(v) else max_iterations
+        return max(1, min(nit, max_iterations))
+
+    @staticmethod
+    def iterate(counts, n_iterations: int, state: dict | None = None, N: int | None = None, min_inliers=20,
+                max_iterations=300, probability=0.99):
+        """Sim3Solver::iterate (Sim3Solver.cc:205-297) replayed over the per-hypothesis inlier counts:
+        `>= mnBestInliers` updates the best, `> mRansacMinInliers` returns. state carries mnIterations /
+        mnBestInliers between calls (None starts a solver of N correspondences). Returns
+        (hit, bNoMore, nInliers, state): hit = index of the hypothesis whose Sim3 is returned, or -1;
+        state["best"] = index of the best hypothesis so far (GetEstimated*), or -1."""
+        if state is None:
+            state = {"N": int(N), "its": 0, "best_inliers": 0, "best": -1,
+                     "max_its": Sim3Solver.ransac_iterations(int(N), probability, min_inliers, max_iterations)}
+        if state["N"] < min_inliers:
+            return -1, True, 0, state
+        cur = 0
+        while state["its"] < state["max_its"] and cur < n_iterations:
+            cur += 1
+            h = state["its"]
+            state["its"] += 1
+            c = int(counts[h])
+            if c >= state["best_inliers"]:
+                state["best_inliers"], state["best"] = c, h
+                if c > min_inliers:
+                    return h, False, c, state
+        return -1, state["its"] >= state["max_its"], 0, state

@@ -799,3 +799,61 @@ def sim3_pair_problem(seed: int = 80, n: int = 1500, n_points: int = 1300, s12: 
           "desc": mdesc, "flags": flags}
     return {"kf1": k1, "kf1_mp": mp1, "kf2": k2, "kf2_mp": mp2, "map": mp, "s12": np.float32(s12), "R12": R12,
             "t12": t12, "matches12": m12}
+
+
+# ---------------------------------------------------------------------------------------
+# Sim3Solver problem (Sim3Solver.cc:54-147 after the constructor): n correspondences between
+# two keyframes' camera frames, X1c = s12 * R12 * X2c + t12 + noise. Depth-proportional noise
+# (lateral: 0.4 px * scale[octave] at the point's depth; along the ray: 0.2 % of the depth), gross
+# outliers (X1c redrawn), octaves 0-7 by the extractor's features-per-level, thresholds
+# mvnMaxError = (size_t)(9.210 * mvLevelSigma2[octave]) as CheckInliers compares them, a few
+# pairs that satisfy the Sim3 but sit at negative depth in both cameras (Project has no sign
+# test), K2 != K1 on request, and n_hyp triplets drawn without replacement inside each triplet.
+# ---------------------------------------------------------------------------------------
+def sim3_solver_problem(seed: int = 100, n: int = 200, outlier_frac: float = 0.3, fix_scale: bool = True,
+                        n_hyp: int = 300, k2_differs: bool = False, W: int = 1241, H: int = 376):
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, _ = KITTI_CAM
+    K1 = np.array([fx, fy, cx, cy], np.float32)
+    K2 = np.array([fx * 1.08, fy * 1.05, cx + 14.5, cy - 6.25], np.float32) if k2_differs else K1.copy()
+    nl = 8
+    sf = np.ones(nl, np.float32)
+    for i in range(1, nl):
+        sf[i] = np.float32(sf[i - 1] * np.float32(1.2))
+    sigma2 = (sf * sf).astype(np.float32)                       # mvLevelSigma2
+    feat = np.array([434, 362, 302, 251, 209, 175, 145, 122], np.float64)
+    oct1 = rng.choice(nl, size=n, p=feat / feat.sum())
+    oct2 = np.clip(oct1 + rng.integers(-1, 2, n), 0, nl - 1)
+    R12 = _small_rot(rng, 12.0)
+    t12 = rng.normal(0, 0.5, 3)
+    s12 = 1.0 if fix_scale else float(rng.uniform(0.8, 1.25))
+    z = rng.uniform(3, 40, n)
+    X2 = np.stack([(rng.uniform(0, W, n) - K2[0 + 2]) / K2[0] * z, (rng.uniform(0, H, n) - K2[3]) / K2[1] * z, z], 1)
+    X1 = s12 * X2 @ R12.T + t12
+    behind = np.zeros(n, bool)
+    if n >= 20:
+        nb = max(1, n // 50)
+        ib = rng.choice(n, nb, replace=False)
+        behind[ib] = True
+        zb = -rng.uniform(0.5, 3.0, nb)
+        Y = np.stack([rng.uniform(-1, 1, nb) * zb, rng.uniform(-0.3, 0.3, nb) * zb, zb], 1)
+        X1[ib] = Y
+        X2[ib] = (Y - t12) @ R12 / s12
+    def noisy(X, octv, K):
+        d = np.abs(X[:, 2])
+        lat = 0.4 * sf[octv] * d / K[0]
+        return X + np.stack([rng.normal(0, 1, n) * lat, rng.normal(0, 1, n) * lat, rng.normal(0, 1, n) * 0.002 * d], 1)
+    X1 = noisy(X1, oct1, K1)
+    X2 = noisy(X2, oct2, K2)
+    outlier = (rng.random(n) < outlier_frac) & ~behind
+    if n <= 5:
+        outlier[:] = False
+    zo = rng.uniform(3, 40, n)
+    Xo = np.stack([(rng.uniform(0, W, n) - K1[2]) / K1[0] * zo, (rng.uniform(0, H, n) - K1[3]) / K1[1] * zo, zo], 1)
+    X1[outlier] = Xo[outlier]
+    trip = np.argsort(rng.random((n_hyp, n)), axis=1)[:, :3].astype(np.int32)
+    thr = lambda o: np.floor(9.210 * sigma2[o].astype(np.float64)).astype(np.float32)
+    return {"X1c": X1.astype(np.float32), "X2c": X2.astype(np.float32), "max_err1": thr(oct1), "max_err2": thr(oct2),
+            "K1": K1, "K2": K2, "fix_scale": bool(fix_scale), "triplets": np.ascontiguousarray(trip),
+            "oct1": oct1.astype(np.int32), "oct2": oct2.astype(np.int32), "R12": R12, "t12": t12, "s12": s12,
+            "outlier": outlier, "behind": behind}
