@@ -658,6 +658,64 @@ int orbs_stage(orbs_engine *e, int slot, const orbs_problem *p);
 int orbs_run_batch(orbs_engine *e, int n_slots, void *stream);
 int orbs_fetch(orbs_engine *e, int slot, orbs_result *r);
 
+/* -------- Optimizer::OptimizeSim3 (the Sim3 refinement of LoopClosing::ComputeSim3) -------- */
+
+/* The graph Optimizer::OptimizeSim3 (Optimizer.h:116, Optimizer.cc:1405-1637) builds: one
+ * VertexSim3Expmap (g2oS12) and, for every pair the reference adds edges for (:1469-1566: a non-null
+ * vpMatches1[i], both map points good, i2 >= 0), compacted by the caller in vnIndexEdge order, an
+ * EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ on fixed points. Host pointers. */
+typedef struct {
+    int32_t n;                    /* nCorrespondences: vnIndexEdge.size() */
+    const float *X1c, *X2c;       /* [n][3] P3D1c / P3D2c (:1492-1503), the float products cv::Mat computes */
+    const float *obs1, *obs2;     /* [n][2] mvKeysUn[i].pt of pKF1 / mvKeysUn[i2].pt of pKF2 (:1521-1549) */
+    const float *inv_sigma2_1, *inv_sigma2_2;   /* [n] mvInvLevelSigma2[kpUn.octave] (:1534, :1556) */
+    float K1[4], K2[4];           /* fx fy cx cy of pKF1->mK / pKF2->mK (:1439-1446) */
+    double q[4], t[3], s;         /* g2oS12 (:1435): rotation (x, y, z, w) as it stands -- the library does
+                                     not normalise it --, translation, scale */
+    float th2;                    /* :1405 (LoopClosing passes 10); deltaHuber = (float)sqrt(th2) (:1464) */
+    int32_t fix_scale;            /* bFixScale -> vSim3->_fix_scale (:1434) */
+} orbo_problem;
+
+typedef struct {
+    double q[4], t[3], s;         /* g2oS12 after the call (:1634); the input, bit for bit, where the
+                                     reference returns before writing it (:1605-1606, n == 0) */
+    int32_t n_inliers;            /* the return value: nIn (:1636) or 0 (:1606) */
+    uint8_t *state;               /* [n] caller-allocated: 0 = kept, 1 = removed after the first optimize
+                                     (:1583-1594), 2 = removed by the final check (:1622-1626); nonzero
+                                     <=> the reference nulls vpMatches1[vnIndexEdge[k]] */
+    int32_t iterations[2];        /* LM iterations of optimize(5) (:1571) and of the second optimize
+                                     (:1611); -1 = not run */
+    double *chi2;                 /* [n][2] caller-allocated or NULL: the last e12->chi2(), e21->chi2()
+                                     of every pair (a removed pair keeps its value at removal) */
+} orbo_result;
+
+typedef struct orbo_engine orbo_engine;
+
+/* As orbs_*: the engine is a host object until a call whose arguments passed every check needs the
+ * device; orbo_create / orbo_reserve succeed without a GPU and every argument error is returned
+ * before the device is touched. */
+int orbo_create(orbo_engine **out);
+void orbo_destroy(orbo_engine *e);
+/* Optimizer::OptimizeSim3 (Optimizer.cc:1405-1637), the whole function in one launch (one workgroup,
+ * no host round trip): optimize(5) (:1571) by g2o's Levenberg-Marquardt on the 7x7 system with
+ * Eigen::LDLT, the Jacobians of both edges by g2o's central differences at 1e-9
+ * (base_binary_edge.hpp:131-205; the edges' own linearizeOplus is commented out), Huber kernels of
+ * width (float)sqrt(th2); pairs with e12->chi2() > th2 || e21->chi2() > th2 on g2o's last evaluated
+ * _error removed (:1575-1595); 0 returned with g2oS12 untouched when fewer than 10 pairs remain
+ * (:1605-1606); else optimize(nBad > 0 ? 10 : 5) (:1598-1611) and the final count (:1614-1629).
+ * n == 0 returns 0 inliers and the input Sim3; 1 <= n < 10 still runs the first optimize and
+ * reports its removals. ORBX_EINVAL: a NULL pointer, n < 0, a bad slot, non-finite q / t / s or
+ * s <= 0. */
+int orbo_optimize_sim3(orbo_engine *e, const orbo_problem *p, orbo_result *r);
+/* Batched device-resident form (the candidates of one LoopClosing::ComputeSim3 call,
+ * LoopClosing.cc:378-456): stage each problem into a slot, one launch solves every slot, fetch per
+ * slot. orbo_stage returns ORBX_ECAP for n > cap_pairs. Results do not depend on the slot or on
+ * the other slots, and repeat bit for bit. */
+int orbo_reserve(orbo_engine *e, int n_slots, int cap_pairs);
+int orbo_stage(orbo_engine *e, int slot, const orbo_problem *p);
+int orbo_run_batch(orbo_engine *e, int n_slots, void *stream);
+int orbo_fetch(orbo_engine *e, int slot, orbo_result *r);
+
 /* -------- local bundle adjustment (replaces Optimizer::LocalBundleAdjustment) -------- */
 
 /* The graph Optimizer::LocalBundleAdjustment (Optimizer.cc:646-898) builds from the map,

@@ -315,8 +315,26 @@ private:
 // keyframes / fixed keyframes / local map points / observations into lba_problem
 // (Optimizer.cc:646-898 order) and applies the result (SetPose / SetWorldPos /
 // EraseMapPointMatch, :977-1048).
+struct Sim3KeyFrame;
+struct Sim3Match;
+struct Sim3;
+
 class Optimizer {
 public:
+    // Optimizer::OptimizeSim3 (Optimizer.h:186, Optimizer.cc:1405-1637) over the POD views the Sim3Solver
+    // takes: vpMatches1[i] is keypoint i of pKF1 (pMP1 = its map point, pMP2 = the match). Edges are added
+    // for the entries the reference adds them for (:1471-1512: pMP2 and pMP1 non-NULL, neither bad,
+    // indexKF2 >= 0), the whole two-stage optimisation runs on the GPU (orbo_*), removed matches are
+    // nulled (pMP2 = false) and g2oS12 is written exactly where the reference writes it: not on the
+    // `return 0` of :1605-1606. Returns nIn. Defined below Sim3Solver.
+    static int OptimizeSim3(const Sim3KeyFrame &pKF1, const Sim3KeyFrame &pKF2, std::vector<Sim3Match> &vpMatches1,
+                            Sim3 &g2oS12, const float th2, const bool bFixScale);
+    // The same for every candidate pKF2 of one LoopClosing::ComputeSim3 call in one launch (as
+    // Sim3Solver::EvaluateAll): vnInliers[c] = OptimizeSim3(pKF1, *vpKF2[c], *vvpMatches1[c], vg2oS12[c], ..).
+    static void OptimizeSim3All(const Sim3KeyFrame &pKF1, const std::vector<const Sim3KeyFrame *> &vpKF2,
+                                const std::vector<std::vector<Sim3Match> *> &vvpMatches1, std::vector<Sim3> &vg2oS12,
+                                const float th2, const bool bFixScale, std::vector<int> &vnInliers);
+
     static lba_result LocalBundleAdjustment(const lba_problem &graph, bool *pbStopFlag, std::vector<float> &poseTcw,
                                             std::vector<float> &pointXw, std::vector<uint8_t> &edgeErase) {
         static thread_local LbaHandle lba;
@@ -390,6 +408,7 @@ struct Sim3KeyFrame {
     float tcw[3] = {0, 0, 0};                     // GetTranslation()
     float fx = 0, fy = 0, cx = 0, cy = 0;         // mK
     std::vector<float> mvLevelSigma2;
+    std::vector<float> mvInvLevelSigma2;          // Optimizer::OptimizeSim3 (Optimizer.cc:1534, 1556)
 };
 
 // Entry i1 of vpMatched12 with everything the constructor dereferences (Sim3Solver.cc:84-135):
@@ -400,6 +419,92 @@ struct Sim3Match {
     int indexKF1 = -1, indexKF2 = -1;     // GetIndexInKeyFrame(pKF1 / pKF2)
     int octave1 = 0, octave2 = 0;         // mvKeysUn[indexKF].octave
     float Xw1[3] = {0, 0, 0}, Xw2[3] = {0, 0, 0};   // GetWorldPos()
+    // Optimizer::OptimizeSim3 only: pKF1->mvKeysUn[i1].pt and pKF2->mvKeysUn[indexKF2].pt (Optimizer.cc:1522, 1548)
+    float pt1[2] = {0, 0}, pt2[2] = {0, 0};
+};
+
+// g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h:41-290) as a value type: rotation quaternion (x, y, z, w),
+// translation, scale. As in the reference, nothing here normalises the quaternion. With operator*
+// the adapter's mg2oScw = gScm * gSmw (LoopClosing.cc:459) needs no g2o.
+struct Sim3 {
+    double q[4] = {0, 0, 0, 1};
+    double t[3] = {0, 0, 0};
+    double s = 1.;
+
+    Sim3() {}
+    // Sim3(const Quaterniond &r, const Vector3d &t, double s) (sim3.h:59-62); r = (x, y, z, w)
+    static Sim3 FromQuaternion(const double r[4], const double t_[3], double s_) {
+        Sim3 S;
+        for (int k = 0; k < 4; k++) S.q[k] = r[k];
+        for (int k = 0; k < 3; k++) S.t[k] = t_[k];
+        S.s = s_;
+        return S;
+    }
+    // Sim3(const Matrix3d &R, const Vector3d &t, double s) (sim3.h:64-67): r = Eigen::Quaterniond(R), R row-major
+    Sim3(const double R[9], const double t_[3], double s_) : s(s_) {
+        for (int k = 0; k < 3; k++) t[k] = t_[k];
+        const double *m = R;
+        double tr = m[0] + m[4] + m[8];
+        if (tr > 0) {
+            tr = std::sqrt(tr + 1.0);
+            q[3] = 0.5 * tr;
+            tr = 0.5 / tr;
+            q[0] = (m[7] - m[5]) * tr;
+            q[1] = (m[2] - m[6]) * tr;
+            q[2] = (m[3] - m[1]) * tr;
+        } else {
+            int i = 0;
+            if (m[4] > m[0]) i = 1;
+            if (m[8] > m[4 * i]) i = 2;
+            const int j = (i + 1) % 3, k = (j + 1) % 3;
+            tr = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+            q[i] = 0.5 * tr;
+            tr = 0.5 / tr;
+            q[3] = (m[3 * k + j] - m[3 * j + k]) * tr;
+            q[j] = (m[3 * j + i] + m[3 * i + j]) * tr;
+            q[k] = (m[3 * k + i] + m[3 * i + k]) * tr;
+        }
+    }
+
+    const double *rotation() const { return q; }      // (x, y, z, w)
+    const double *translation() const { return t; }
+    double scale() const { return s; }
+
+    // Eigen's Quaternion * Vector3 (_transformVector)
+    static void Rotate(const double r[4], const double v[3], double o[3]) {
+        double uv[3] = {r[1] * v[2] - r[2] * v[1], r[2] * v[0] - r[0] * v[2], r[0] * v[1] - r[1] * v[0]};
+        uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+        const double cx = r[1] * uv[2] - r[2] * uv[1], cy = r[2] * uv[0] - r[0] * uv[2], cz = r[0] * uv[1] - r[1] * uv[0];
+        o[0] = v[0] + r[3] * uv[0] + cx;
+        o[1] = v[1] + r[3] * uv[1] + cy;
+        o[2] = v[2] + r[3] * uv[2] + cz;
+    }
+    void map(const double xyz[3], double out[3]) const {   // s * (r * xyz) + t
+        double p[3];
+        Rotate(q, xyz, p);
+        for (int k = 0; k < 3; k++) out[k] = s * p[k] + t[k];
+    }
+    Sim3 inverse() const {   // Sim3(r.conjugate(), r.conjugate() * ((-1. / s) * t), 1. / s)
+        Sim3 r;
+        r.q[0] = -q[0]; r.q[1] = -q[1]; r.q[2] = -q[2]; r.q[3] = q[3];
+        const double f = -1. / s;
+        const double v[3] = {f * t[0], f * t[1], f * t[2]};
+        Rotate(r.q, v, r.t);
+        r.s = 1. / s;
+        return r;
+    }
+    Sim3 operator*(const Sim3 &o) const {
+        Sim3 r;
+        r.q[3] = q[3] * o.q[3] - q[0] * o.q[0] - q[1] * o.q[1] - q[2] * o.q[2];
+        r.q[0] = q[3] * o.q[0] + q[0] * o.q[3] + q[1] * o.q[2] - q[2] * o.q[1];
+        r.q[1] = q[3] * o.q[1] + q[1] * o.q[3] + q[2] * o.q[0] - q[0] * o.q[2];
+        r.q[2] = q[3] * o.q[2] + q[2] * o.q[3] + q[0] * o.q[1] - q[1] * o.q[0];
+        double p[3];
+        Rotate(q, o.t, p);
+        for (int k = 0; k < 3; k++) r.t[k] = s * p[k] + t[k];
+        r.s = s * o.s;
+        return r;
+    }
 };
 
 // Sim3Solver with the reference's members over POD keyframe views. The RANSAC body runs on the GPU:
@@ -563,6 +668,7 @@ public:
     }
 
 private:
+    friend class Optimizer;   // OptimizeSim3 computes P3D1c / P3D2c with ToCamera
     struct Engine {
         orbs_engine *h = nullptr;
         Engine() { check(orbs_create(&h), "orbs_create"); }
@@ -644,5 +750,95 @@ private:
     std::vector<uint64_t> mvInlierBits;
     std::vector<float> mvRotation, mvTranslation, mvScale;
 };
+
+namespace detail {
+// the edges of one OptimizeSim3 call (Optimizer.cc:1469-1566), compacted in vnIndexEdge order
+struct Sim3OptGraph {
+    std::vector<size_t> vnIndexEdge;
+    std::vector<float> X1c, X2c, obs1, obs2, inv1, inv2;
+    std::vector<uint8_t> state;
+    orbo_problem Problem(const Sim3KeyFrame &pKF1, const Sim3KeyFrame &pKF2, const Sim3 &g2oS12, float th2, bool bFixScale) {
+        orbo_problem p{};
+        p.n = (int32_t)vnIndexEdge.size();
+        p.X1c = X1c.data(); p.X2c = X2c.data();
+        p.obs1 = obs1.data(); p.obs2 = obs2.data();
+        p.inv_sigma2_1 = inv1.data(); p.inv_sigma2_2 = inv2.data();
+        p.K1[0] = pKF1.fx; p.K1[1] = pKF1.fy; p.K1[2] = pKF1.cx; p.K1[3] = pKF1.cy;
+        p.K2[0] = pKF2.fx; p.K2[1] = pKF2.fy; p.K2[2] = pKF2.cx; p.K2[3] = pKF2.cy;
+        for (int k = 0; k < 4; k++) p.q[k] = g2oS12.q[k];
+        for (int k = 0; k < 3; k++) p.t[k] = g2oS12.t[k];
+        p.s = g2oS12.s;
+        p.th2 = th2;
+        p.fix_scale = bFixScale ? 1 : 0;
+        return p;
+    }
+};
+struct Sim3OptEngine {
+    orbo_engine *h = nullptr;
+    Sim3OptEngine() { check(orbo_create(&h), "orbo_create"); }
+    ~Sim3OptEngine() { orbo_destroy(h); }
+};
+}  // namespace detail
+
+inline void Optimizer::OptimizeSim3All(const Sim3KeyFrame &pKF1, const std::vector<const Sim3KeyFrame *> &vpKF2,
+                                       const std::vector<std::vector<Sim3Match> *> &vvpMatches1, std::vector<Sim3> &vg2oS12,
+                                       const float th2, const bool bFixScale, std::vector<int> &vnInliers) {
+    static thread_local detail::Sim3OptEngine eng;
+    const size_t nc = vpKF2.size();
+    if (vvpMatches1.size() != nc || vg2oS12.size() != nc) throw std::runtime_error("OptimizeSim3All: size mismatch");
+    vnInliers.assign(nc, 0);
+    if (!nc) return;
+    std::vector<detail::Sim3OptGraph> graphs(nc);
+    int cap = 0;
+    for (size_t c = 0; c < nc; c++) {
+        detail::Sim3OptGraph &g = graphs[c];
+        const Sim3KeyFrame &pKF2 = *vpKF2[c];
+        const std::vector<Sim3Match> &vpMatches1 = *vvpMatches1[c];
+        const int N = (int)vpMatches1.size();
+        for (int i = 0; i < N; i++) {
+            const Sim3Match &m = vpMatches1[i];
+            if (!m.pMP2) continue;                                // :1471
+            if (!m.pMP1) continue;                                // :1485, 1511
+            if (m.bad1 || m.bad2 || m.indexKF2 < 0) continue;     // :1487, 1508
+            Sim3Solver::ToCamera(pKF1, m.Xw1, g.X1c);             // P3D1c = R1w * P3D1w + t1w
+            Sim3Solver::ToCamera(pKF2, m.Xw2, g.X2c);
+            g.obs1.push_back(m.pt1[0]); g.obs1.push_back(m.pt1[1]);
+            g.obs2.push_back(m.pt2[0]); g.obs2.push_back(m.pt2[1]);
+            g.inv1.push_back(pKF1.mvInvLevelSigma2[m.octave1]);
+            g.inv2.push_back(pKF2.mvInvLevelSigma2[m.octave2]);
+            g.vnIndexEdge.push_back((size_t)i);
+        }
+        cap = std::max(cap, (int)g.vnIndexEdge.size());
+    }
+    check(orbo_reserve(eng.h, (int)nc, cap), "orbo_reserve");
+    for (size_t c = 0; c < nc; c++) {
+        const orbo_problem p = graphs[c].Problem(pKF1, *vpKF2[c], vg2oS12[c], th2, bFixScale);
+        check(orbo_stage(eng.h, (int)c, &p), "orbo_stage");
+    }
+    check(orbo_run_batch(eng.h, (int)nc, nullptr), "orbo_run_batch");
+    for (size_t c = 0; c < nc; c++) {
+        detail::Sim3OptGraph &g = graphs[c];
+        g.state.assign(std::max<size_t>(g.vnIndexEdge.size(), 1), 0);
+        orbo_result r{};
+        r.state = g.state.data();
+        check(orbo_fetch(eng.h, (int)c, &r), "orbo_fetch");
+        for (size_t k = 0; k < g.vnIndexEdge.size(); k++)
+            if (g.state[k]) (*vvpMatches1[c])[g.vnIndexEdge[k]].pMP2 = false;   // vpMatches1[idx] = NULL (:1587, 1625)
+        if (r.iterations[1] >= 0)                                               // past the `return 0` of :1605-1606
+            vg2oS12[c] = Sim3::FromQuaternion(r.q, r.t, r.s);                            // g2oS12 = vSim3_recov->estimate()
+        vnInliers[c] = r.n_inliers;
+    }
+}
+
+inline int Optimizer::OptimizeSim3(const Sim3KeyFrame &pKF1, const Sim3KeyFrame &pKF2, std::vector<Sim3Match> &vpMatches1,
+                                   Sim3 &g2oS12, const float th2, const bool bFixScale) {
+    std::vector<const Sim3KeyFrame *> vpKF2{&pKF2};
+    std::vector<std::vector<Sim3Match> *> vvp{&vpMatches1};
+    std::vector<Sim3> vS{g2oS12};
+    std::vector<int> vn;
+    OptimizeSim3All(pKF1, vpKF2, vvp, vS, th2, bFixScale, vn);
+    g2oS12 = vS[0];
+    return vn[0];
+}
 
 }  // namespace orbslam2_amd

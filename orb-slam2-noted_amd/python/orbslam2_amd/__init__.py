@@ -166,6 +166,13 @@ SIGNATURES = [
     ("orbs_stage", _I, [_P, _I, _P]),
     ("orbs_run_batch", _I, [_P, _I, _P]),
     ("orbs_fetch", _I, [_P, _I, _P]),
+    ("orbo_create", _I, [C.POINTER(C.c_void_p)]),
+    ("orbo_destroy", None, [_P]),
+    ("orbo_optimize_sim3", _I, [_P, _P, _P]),
+    ("orbo_reserve", _I, [_P, _I, _I]),
+    ("orbo_stage", _I, [_P, _I, _P]),
+    ("orbo_run_batch", _I, [_P, _I, _P]),
+    ("orbo_fetch", _I, [_P, _I, _P]),
 ]
 
 
@@ -1506,3 +1513,108 @@ class Sim3Solver:
                 if c > min_inliers:
                     return h, False, c, state
         return -1, state["its"] >= state["max_its"], 0, state
+
+
+# ---- Optimizer::OptimizeSim3 (orbo_*): the Sim3 refinement of LoopClosing::ComputeSim3 --------
+class OrboProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("X1c", C.c_void_p), ("X2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
+                ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("th2", C.c_float),
+                ("fix_scale", C.c_int32)]
+
+
+class OrboResult(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("n_inliers", C.c_int32),
+                ("state", C.c_void_p), ("iterations", C.c_int32 * 2), ("chi2", C.c_void_p)]
+
+
+_ORBO_ARRAYS = ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")
+
+
+def orbo_problem(prob: dict):
+    """(OrboProblem, arrays it points into) of a dict shaped like synth.optimize_sim3_problem."""
+    keep = {k: np.ascontiguousarray(prob[k], np.float32) for k in _ORBO_ARRAYS}
+    P = OrboProblem()
+    P.n = len(keep["X1c"])
+    for k in _ORBO_ARRAYS:
+        setattr(P, k, keep[k].ctypes.data)
+    P.K1[:] = [float(v) for v in np.asarray(prob["K1"], np.float32)]
+    P.K2[:] = [float(v) for v in np.asarray(prob["K2"], np.float32)]
+    P.q[:] = [float(v) for v in np.asarray(prob["q"], np.float64)]
+    P.t[:] = [float(v) for v in np.asarray(prob["t"], np.float64)]
+    P.s = float(prob["s"])
+    P.th2 = float(np.float32(prob["th2"]))
+    P.fix_scale = 1 if prob["fix_scale"] else 0
+    return P, keep
+
+
+class Sim3Optimizer:
+    """Optimizer::OptimizeSim3 (Optimizer.h:186) on the GPU: both optimize() calls, the outlier removal
+    between them and the final count in one launch, one workgroup per problem. Problems are dicts
+    shaped like synth.optimize_sim3_problem: {"X1c", "X2c", "obs1", "obs2", "inv_sigma2_1",
+    "inv_sigma2_2", "K1", "K2", "q" (x, y, z, w), "t", "s", "th2", "fix_scale"}. Results: {"q", "t", "s"
+    (float64, g2oS12 after the call), "n_inliers", "state" [n] (0 kept, 1 removed after the first
+    optimize, 2 removed by the final check), "iterations" (2), "chi2" [n, 2]}."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        _check(lib().orbo_create(C.byref(h)), "orbo_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orbo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _result(n):
+        state = np.zeros(max(n, 1), np.uint8)
+        chi2 = np.zeros((max(n, 1), 2), np.float64)
+        R = OrboResult()
+        R.state = state.ctypes.data
+        R.chi2 = chi2.ctypes.data
+        return R, (state, chi2)
+
+    @staticmethod
+    def _pack(R, bufs, n):
+        return {"q": np.array(R.q[:], np.float64), "t": np.array(R.t[:], np.float64), "s": np.float64(R.s),
+                "n_inliers": int(R.n_inliers), "state": bufs[0][:n].copy(), "iterations": tuple(R.iterations),
+                "chi2": bufs[1][:n].copy()}
+
+    def optimize(self, prob: dict) -> dict:
+        P, keep = orbo_problem(prob)
+        R, bufs = self._result(P.n)
+        _check(lib().orbo_optimize_sim3(self._h, C.byref(P), C.byref(R)), "orbo_optimize_sim3")
+        return self._pack(R, bufs, P.n)
+
+    def reserve(self, n_slots: int, cap_pairs: int):
+        _check(lib().orbo_reserve(self._h, n_slots, cap_pairs), "orbo_reserve")
+
+    def stage(self, slot: int, prob: dict):
+        P, keep = orbo_problem(prob)
+        _check(lib().orbo_stage(self._h, slot, C.byref(P)), "orbo_stage")
+
+    def run_batch(self, n_slots: int, stream=None):
+        _check(lib().orbo_run_batch(self._h, n_slots, stream), "orbo_run_batch")
+
+    def fetch(self, slot: int, n: int) -> dict:
+        R, bufs = self._result(n)
+        _check(lib().orbo_fetch(self._h, slot, C.byref(R)), "orbo_fetch")
+        return self._pack(R, bufs, n)
+
+    def optimize_batch(self, probs) -> list:
+        """Every problem of `probs` in one launch (the candidates of one ComputeSim3 call)."""
+        probs = list(probs)
+        if not probs:
+            return []
+        self.reserve(len(probs), max(len(p["X1c"]) for p in probs))
+        for s, p in enumerate(probs):
+            self.stage(s, p)
+        self.run_batch(len(probs))
+        return [self.fetch(s, len(p["X1c"])) for s, p in enumerate(probs)]

@@ -857,3 +857,81 @@ def sim3_solver_problem(seed: int = 100, n: int = 200, outlier_frac: float = 0.3
             "K1": K1, "K2": K2, "fix_scale": bool(fix_scale), "triplets": np.ascontiguousarray(trip),
             "oct1": oct1.astype(np.int32), "oct2": oct2.astype(np.int32), "R12": R12, "t12": t12, "s12": s12,
             "outlier": outlier, "behind": behind}
+
+
+# ---------------------------------------------------------------------------------------
+# Optimizer::OptimizeSim3 problem (Optimizer.cc:1469-1566 after the edge loop): n pairs of
+# camera-frame points, X1c = s12 * R12 * X2c + t12, at 5-30 m depth in camera 2 under a KITTI-like
+# K; observations = the points' own projections + N(0, 0.6 px * scale[octave]) per axis, octaves
+# 0-7 by the extractor's features-per-level, information 1 / sigma2[octave] as a float; a fraction
+# of gross outliers whose obs2 is displaced by 8-40 px; the start g2oS12 = the true Sim3 with
+# ~0.01 rad, ~0.1 m and (free scale only) ~3 % of error, its rotation a unit quaternion
+# (x, y, z, w) up to rounding. Everything the ABI takes as float is rounded through float32.
+# ---------------------------------------------------------------------------------------
+def _quat_xyzw(R):
+    """Unit quaternion (x, y, z, w) of a rotation matrix, w >= 0."""
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    if w > 1e-6:
+        q = np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        t = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+        q = np.zeros(4)
+        q[i] = 0.5 * t
+        q[3] = (R[k, j] - R[j, k]) * 0.5 / t
+        q[j] = (R[j, i] + R[i, j]) * 0.5 / t
+        q[k] = (R[k, i] + R[i, k]) * 0.5 / t
+    return q / np.linalg.norm(q)
+
+
+def optimize_sim3_problem(seed: int = 500, n: int = 200, fix_scale: bool = True, outlier_frac: float = 0.2,
+                          noise: float = 0.6, k2_differs: bool = False, n_outliers: int | None = None,
+                          th2: float = 10.0, W: int = 1241, H: int = 376):
+    """n_outliers fixes the number of gross outliers (else round(outlier_frac * n))."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, _ = KITTI_CAM
+    K1 = np.array([fx, fy, cx, cy], np.float32)
+    K2 = np.array([fx * 1.08, fy * 1.05, cx + 14.5, cy - 6.25], np.float32) if k2_differs else K1.copy()
+    nl = 8
+    sf = np.ones(nl, np.float32)
+    for i in range(1, nl):
+        sf[i] = np.float32(sf[i - 1] * np.float32(1.2))
+    inv_sigma2 = (np.float32(1) / (sf * sf)).astype(np.float32)      # mvInvLevelSigma2
+    feat = np.array([434, 362, 302, 251, 209, 175, 145, 122], np.float64)
+    oct1 = rng.choice(nl, size=n, p=feat / feat.sum())
+    oct2 = np.clip(oct1 + rng.integers(-1, 2, n), 0, nl - 1)
+    R12 = _small_rot(rng, 6.0)
+    t12 = rng.normal(0, 0.4, 3)
+    s12 = 1.0 if fix_scale else float(rng.uniform(0.85, 1.2))
+    z = rng.uniform(5, 30, n)
+    K2d = K2.astype(np.float64)
+    X2 = np.stack([(rng.uniform(60, W - 60, n) - K2d[2]) / K2d[0] * z, (rng.uniform(40, H - 40, n) - K2d[3]) / K2d[1] * z, z], 1)
+    X1 = s12 * X2 @ R12.T + t12
+    X1f, X2f = X1.astype(np.float32), X2.astype(np.float32)
+
+    def observe(X, K, octv):
+        X = X.astype(np.float64)
+        K = K.astype(np.float64)
+        sig = noise * sf[octv].astype(np.float64)
+        return np.stack([K[0] * X[:, 0] / X[:, 2] + K[2] + rng.normal(0, 1, n) * sig,
+                         K[1] * X[:, 1] / X[:, 2] + K[3] + rng.normal(0, 1, n) * sig], 1)
+
+    obs1 = observe(X1f, K1, oct1)
+    obs2 = observe(X2f, K2, oct2)
+    n_out = int(round(outlier_frac * n)) if n_outliers is None else int(n_outliers)
+    outlier = np.zeros(n, bool)
+    if n_out > 0:
+        outlier[rng.choice(n, n_out, replace=False)] = True
+    ang = rng.uniform(0, 2 * np.pi, n)
+    mag = rng.uniform(8, 40, n) * sf[oct2]
+    obs2[outlier] += (np.stack([np.cos(ang), np.sin(ang)], 1) * mag[:, None])[outlier]
+    dR = _small_rot(rng, 0.6)                                         # ~0.01 rad
+    Rs = dR @ R12
+    ts = t12 + rng.normal(0, 0.06, 3)                                 # ~0.1 m
+    ss = 1.0 if fix_scale else s12 * float(1 + rng.normal(0, 0.03))
+    return {"X1c": X1f, "X2c": X2f, "obs1": obs1.astype(np.float32), "obs2": obs2.astype(np.float32),
+            "inv_sigma2_1": inv_sigma2[oct1], "inv_sigma2_2": inv_sigma2[oct2], "K1": K1, "K2": K2,
+            "q": _quat_xyzw(Rs), "t": ts.astype(np.float64), "s": float(ss), "th2": np.float32(th2),
+            "fix_scale": bool(fix_scale), "oct1": oct1.astype(np.int32), "oct2": oct2.astype(np.int32),
+            "outlier": outlier, "R12": R12, "t12": t12, "s12": s12}
