@@ -131,12 +131,18 @@ void *orbx_stream(orbx_engine *e);
 
 /* Frame::ComputeStereoMatches (include/Frame.h:249, Frame.cc:831-1128) for the frame whose
  * left image was last extracted by `left` and right image by `right` (orbx_extract).
- * mbf = Camera.bf, mb = mbf / fx. Writes mvuRight[n] and mvDepth[n] (-1 = no match). */
+ * mbf = Camera.bf, mb = mbf / fx. Writes mvuRight[n] and mvDepth[n] (-1 = no match).
+ * Limit: the sort of the right keypoints keeps 4 * (2 * (H + 2) + 2 * cap) bytes in LDS (H = image
+ * height, cap = orbx_capacity, about nfeatures + 3 * nlevels) and the call returns ORBX_EINVAL,
+ * launching nothing, when that exceeds 64 KB: H + 2 + cap <= 8192, i.e. up to about 7.7k keypoint
+ * slots per image (7686 features at 8 levels and 480 rows, 7790 at 376 rows). Extraction itself has
+ * no such limit. */
 int orbm_stereo_match(orbx_engine *left, orbx_engine *right, float mbf, float mb,
                       float *u_right, float *depth, int n);
 
 /* Batched stereo over the engine's last device batch: image 2p = left, 2p+1 = right of
- * pair p. Results stay on device: u_right / depth [n_pairs][cap]. */
+ * pair p. Results stay on device: u_right / depth [n_pairs][cap]. The same limit as
+ * orbm_stereo_match applies (ORBX_EINVAL when H + 2 + cap > 8192). */
 int orbm_stereo_match_batch_device(orbx_engine *e, int n_pairs, float mbf, float mb, void *stream);
 
 /* Provenance: 16 hex digits of SHA-256 over the library's sources (tools/src_hash.py), baked in

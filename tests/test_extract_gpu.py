@@ -7,6 +7,7 @@ image pyramid must be identical to the oracle's on the same seeded inputs.
 import numpy as np
 import pytest
 
+import frontend_cases as fc
 from orbslam2_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -96,18 +97,88 @@ def test_extract_noise_many_candidates(amd, oracle_mod):
 
 
 @pytest.mark.parametrize("env", [{"ORBX_QT_LDS_KB": "16"}, {"ORBX_QT_LDS_KB": "160"},
-                                 {"ORBX_QT_NODES_LDS": "1", "ORBX_QT_LDS_KB": "96"}])
+                                 {"ORBX_QT_NODES_LDS": "1", "ORBX_QT_LDS_KB": "96"},
+                                 {"ORBX_QT_LDS_KB": "16", "fast": (12, 7)}])
 def test_extract_quadtree_layouts(amd, oracle_mod, monkeypatch, env):
     """The quadtree's memory layouts (read when an engine sizes its geometry): keys in global
     scratch for levels above a 16 KB LDS budget, every level in LDS at 160 KB, node arrays in LDS;
-    each with its rank-sort stage (the idle key buffer, or the key area) -- all bit-exact."""
+    each with its rank-sort stage (the idle key buffer, or the key area) -- all bit-exact. The case
+    with "fast" runs the global-scratch key path at those thresholds on the low-contrast copy of the
+    textured image, where the cells that retry at minThFAST supply >= 100 keypoints."""
+    ini, mn = env.get("fast", (20, 7))
     for k, v in env.items():
-        monkeypatch.setenv(k, v)
+        if k.startswith("ORBX_"):
+            monkeypatch.setenv(k, v)
     rng = np.random.default_rng(8)
-    for img in (synth.textured_image(376, 1241, 31), rng.integers(0, 256, size=(376, 1241), dtype=np.uint8)):
-        ex = amd.ORBextractor(2000, 1.2, 8, 20, 7)
-        ref = oracle_mod.Extractor(2000, 1.2, 8, 20, 7)
-        _assert_same_kps(ex(img), ref.extract(img), str(env))
+    imgs = (synth.textured_image(376, 1241, 31), rng.integers(0, 256, size=(376, 1241), dtype=np.uint8))
+    if "fast" in env:
+        imgs = (fc.low_contrast(imgs[0]),)
+    for img in imgs:
+        ex = amd.ORBextractor(2000, 1.2, 8, ini, mn)
+        ref = oracle_mod.Extractor(2000, 1.2, 8, ini, mn)
+        want = ref.extract(img)
+        if "fast" in env:   # both FAST passes supply keypoints
+            assert (want[0]["response"] < ini).sum() >= 100 and (want[0]["response"] >= ini).sum() >= 100
+        _assert_same_kps(ex(img), want, str(env))
+
+
+# (iniThFAST, minThFAST): the shipped pairs, ini == min, ini < min, and the edges of cv::FAST's
+# clamp to [0, 255] (the kernels and the oracle clamp alike)
+THRESHOLDS = [(20, 7), (12, 7), (7, 7), (30, 10), (40, 39), (7, 20), (0, 0), (1, 0), (255, 7), (254, 253),
+              (300, -5)]
+
+
+@pytest.fixture(scope="module")
+def sweep_images():
+    img = synth.textured_image(240, 320, 23)
+    return {"textured": img, "low_contrast": fc.low_contrast(img)}
+
+
+def test_extract_threshold_sweep(amd, oracle_mod, sweep_images):
+    """One NMS at min(ini, min) serves both FAST passes and the quadtree kernel picks a threshold per
+    cell: every (ini, min) pair on a textured 240 x 320 image (few retried cells) and on its
+    low-contrast copy (most keypoints from retried cells; test_frontend_cases_cpu.py), all seven
+    keypoint fields and the descriptors bit for bit. The smallest level is 67 x 89. No pixel of
+    either image passes FAST at 253: (254, 253) gives 0 keypoints. Thresholds outside [0, 255]
+    behave as clamped: (300, -5) equals (255, 0), whose every keypoint comes from a retried cell."""
+    for name, img in sweep_images.items():
+        got = {}
+        for ini, mn in THRESHOLDS + [(255, 0)]:
+            got[ini, mn] = amd.ORBextractor(500, 1.2, 8, ini, mn)(img)
+            _assert_same_kps(got[ini, mn], oracle_mod.Extractor(500, 1.2, 8, ini, mn).extract(img), f"{name} {ini}/{mn}")
+        assert len(got[254, 253][0]) == 0
+        assert len(got[255, 0][0]) > 100
+        _assert_same_kps(got[300, -5], got[255, 0], f"{name} 300/-5 against 255/0")
+        assert got[20, 7][0].tobytes() != got[30, 10][0].tobytes()
+
+
+@pytest.mark.parametrize("ini,mn", [(12, 7), (30, 10), (0, 0)])
+def test_extract_threshold_sweep_batch(amd, oracle_mod, sweep_images, ini, mn):
+    """The batched device path builds its geometry (thresholds included) separately: both sweep
+    images in one batch of 2."""
+    import torch
+    imgs = np.stack(list(sweep_images.values()))
+    h, w = imgs.shape[1:]
+    dev = torch.from_numpy(imgs).cuda()
+    ex = amd.BatchExtractor(500, 1.2, 8, ini, mn)
+    ex.reserve(w, h, 2)
+    torch.cuda.synchronize()
+    ex.extract_device(dev.data_ptr(), 2, w, h, w, h * w)
+    ref = oracle_mod.Extractor(500, 1.2, 8, ini, mn)
+    for i in range(2):
+        _assert_same_kps(ex.fetch(i), ref.extract(imgs[i]), f"batch[{i}] {ini}/{mn}")
+
+
+@pytest.mark.parametrize("name,h,w,nf,ini,mn,seed", [
+    ("kitti04", 370, 1226, 2000, 12, 7, 21),     # Stereo/KITTI04-12.yaml thresholds at its sequences' size
+    ("mono_init", 376, 1241, 4000, 20, 7, 31),   # mpIniORBextractor: 2 * nFeatures (Tracking.cc:190)
+])
+def test_extract_shipped_configs(amd, oracle_mod, name, h, w, nf, ini, mn, seed):
+    img = synth.textured_image(h, w, seed)
+    for tag, im in (("textured", img), ("low_contrast", fc.low_contrast(img))):
+        ex = amd.ORBextractor(nf, 1.2, 8, ini, mn)
+        ref = oracle_mod.Extractor(nf, 1.2, 8, ini, mn)
+        _assert_same_kps(ex(im), ref.extract(im), f"{name} {tag}")
 
 
 def test_extract_flat_and_sparse(amd, oracle_mod):

@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import frontend_cases as fc
 from orbslam2_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -284,3 +285,141 @@ def test_stereo_pipeline_host_mode_varying_batches(amd, oracle_mod):
             _check_pair(outs[b].pair(p), refs[q], f"batch {b} pair {p}")
     torch.cuda.synchronize()
     pl.close()
+
+
+# ---- the shipped cameras, a binding disparity window, zero disparity (inputs: frontend_cases.py,
+# pinned with the oracle alone by test_frontend_cases_cpu.py). All through the two-engine drop-in
+# path ORBextractor x 2 + compute_stereo_matches.
+
+def _drop_in(amd, L, R, nf, ini, mn, ref, what):
+    """Two engines on L and R; their keypoints and descriptors must equal the oracle's (kL, dL, kR,
+    dR = ref[:4]) before any stereo compare, so a failure names the stage that made it."""
+    exL, exR = amd.ORBextractor(nf, 1.2, 8, ini, mn), amd.ORBextractor(nf, 1.2, 8, ini, mn)
+    kL, dL = exL(L)
+    kR, dR = exR(R)
+    assert kL.tobytes() == ref[0].tobytes() and np.array_equal(dL, ref[1]), what + ": left extraction"
+    assert kR.tobytes() == ref[2].tobytes() and np.array_equal(dR, ref[3]), what + ": right extraction"
+    return exL, exR, len(kL)
+
+
+def _assert_same_stereo(got, ref, what):
+    for name, g, r in (("u_right", got[0], ref[0]), ("depth", got[1], ref[1])):
+        assert g.shape == r.shape, f"{what}: {name} count"
+        bad = np.nonzero(g.view(np.uint32) != r.view(np.uint32))[0]
+        assert bad.size == 0, f"{what}: {name} differs at {bad[:8]} got {g[bad[:4]]} want {r[bad[:4]]}"
+
+
+@pytest.mark.parametrize("name,kind", [("kitti04", "wide"), ("euroc", "wide"), ("d435i", "wide"), ("small", "wide"),
+                                       ("kitti04", "dense"), ("euroc", "dense")])
+def test_stereo_shipped_cameras(amd, oracle_mod, name, kind):
+    """Each camera with its own image size (row table of H + 2 entries, sort LDS of 2 * (H + 2) +
+    2 * cap words), feature count, FAST thresholds, bf and mb. "wide": disparities up to 1.15 fx, so
+    `kx >= minU` and `disparity < maxD` both reject; "dense": synth.stereo_pair's 2..96 px."""
+    cam = fc.CAMERAS[name]
+    mb = fc.mb_of(cam.bf, cam.fx)
+    if kind == "wide":
+        L, R, *ref, ((u_ref, d_ref), _) = fc.wide_reference(oracle_mod, name)
+    else:
+        L, R = synth.stereo_pair(cam.h, cam.w, fc.WIDE_SEED)
+        *ref, ((u_ref, d_ref),) = fc.stereo_reference(oracle_mod, L, R, cam.nf, cam.ini, cam.min, cam.bf, (mb,))
+    assert (u_ref >= 0).sum() >= 50
+    exL, exR, n = _drop_in(amd, L, R, cam.nf, cam.ini, cam.min, ref, f"{name} {kind}")
+    _assert_same_stereo(amd.compute_stereo_matches(exL, exR, n, cam.bf, mb), (u_ref, d_ref), f"{name} {kind}")
+
+
+def test_stereo_maxd_binds(amd, oracle_mod):
+    """The "small" camera's wide pair matched with mb and with mb / 4 (maxD = fx and 4 fx): both
+    bit-equal to the oracle, and different from each other in >= 20 entries -- the window test is
+    live on the GPU, not only in the oracle."""
+    cam = fc.CAMERAS["small"]
+    mb = fc.mb_of(cam.bf, cam.fx)
+    L, R, *ref, (ref1, ref4) = fc.wide_reference(oracle_mod, "small")
+    exL, exR, n = _drop_in(amd, L, R, cam.nf, cam.ini, cam.min, ref, "small")
+    got1 = amd.compute_stereo_matches(exL, exR, n, cam.bf, mb)
+    got4 = amd.compute_stereo_matches(exL, exR, n, cam.bf, mb / 4)
+    _assert_same_stereo(got1, ref1, "maxD = fx")
+    _assert_same_stereo(got4, ref4, "maxD = 4 fx")
+    assert (got1[0].view(np.uint32) != got4[0].view(np.uint32)).sum() >= 20
+
+
+def test_stereo_zero_disparity(amd, oracle_mod):
+    """Keypoints on a mirror axis match themselves with SAD(-1) == SAD(+1): disparity exactly 0, the
+    `disparity <= 0` branch (Frame.cc:1092-1096). mvDepth = mbf / 0.01f at exactly the oracle's
+    indices, mvuRight = float(double(uL) - 0.01) there."""
+    L, R = fc.mirror_pair(240, 321, 5)
+    *ref, ((u_ref, d_ref),) = fc.stereo_reference(oracle_mod, L, R, 500, 20, 7, KITTI_BF, (0.537,))
+    exL, exR, n = _drop_in(amd, L, R, 500, 20, 7, ref, "mirror")
+    u, d = amd.compute_stereo_matches(exL, exR, n, KITTI_BF, 0.537)
+    _assert_same_stereo((u, d), (u_ref, d_ref), "mirror")
+    far = np.flatnonzero(d_ref == fc.far_depth(KITTI_BF))
+    assert far.size >= 3
+    np.testing.assert_array_equal(np.flatnonzero(d == fc.far_depth(KITTI_BF)), far)
+    np.testing.assert_array_equal(u[far], (ref[0]["x"][far].astype(np.float64) - 0.01).astype(np.float32))
+
+
+def test_stereo_identical_pair(amd, oracle_mod):
+    """R == L: every match has SAD 0, the median is 0 and the cut `dist < 2.1 * median` keeps none
+    (Frame.cc:1112-1127): all -1, as the oracle."""
+    L = synth.textured_image(240, 320, 23)
+    *ref, ((u_ref, d_ref),) = fc.stereo_reference(oracle_mod, L, L, 500, 20, 7, KITTI_BF, (0.537,))
+    assert (u_ref == -1).all() and (d_ref == -1).all() and len(u_ref) > 100
+    exL, exR, n = _drop_in(amd, L, L, 500, 20, 7, ref, "identical")
+    _assert_same_stereo(amd.compute_stereo_matches(exL, exR, n, KITTI_BF, 0.537), (u_ref, d_ref), "identical")
+
+
+@pytest.mark.parametrize("name", ["euroc", "d435i"])
+def test_stereo_pipeline_shipped_cameras(amd, oracle_mod, name):
+    """StereoPipeline at a shipped camera's size, feature count, thresholds and bf / mb: 3 wide pairs
+    over 2 engines (chunks of 2 and 1), keypoints, descriptors, mvuRight and mvDepth per pair."""
+    import torch
+    cam = fc.CAMERAS[name]
+    mb = fc.mb_of(cam.bf, cam.fx)
+    pairs = [fc.wide_reference(oracle_mod, name)[:2]] + [fc.camera_wide_pair(cam, s) for s in (33, 34)]
+    dev = torch.from_numpy(np.stack([im for pr in pairs for im in pr])).cuda()
+    pl = amd.StereoPipeline(cam.nf, iniThFAST=cam.ini, minThFAST=cam.min, n_engines=2)
+    pl.reserve(cam.w, cam.h, 3)
+    torch.cuda.synchronize()
+    pl.stereo_batch(dev.data_ptr(), 3, cam.w, cam.h, cam.w, cam.h * cam.w, cam.bf, mb)
+    torch.cuda.synchronize()
+    for p, (L, R) in enumerate(pairs):
+        if p == 0:
+            kL, dL, kR, dR, ((u, d), _) = fc.wide_reference(oracle_mod, name)[2:]
+        else:
+            kL, dL, kR, dR, ((u, d),) = fc.stereo_reference(oracle_mod, L, R, cam.nf, cam.ini, cam.min, cam.bf, (mb,))
+        _check_pair((*pl.fetch(p), *[a[:len(kL)] for a in pl.stereo_fetch(p)]), (kL, dL, kR, dR, u, d), f"{name} pair {p}")
+    pl.close()
+
+
+def _capacity(amd, ex):
+    import ctypes
+    cap = ctypes.c_int()
+    assert amd.lib().orbx_capacity(ex.handle, ctypes.byref(cap)) == 0
+    return cap.value
+
+
+def test_stereo_capacity_limit(amd, oracle_mod):
+    """The matcher's documented limit (include/orbslam2_amd.h, orbm_stereo_match): the right-keypoint
+    sort keeps 2 * (H + 2) + 2 * capacity words in LDS and refuses more than 64 KB with ORBX_EINVAL
+    (status -1). At 752 x 480 the capacity is nfeatures + 24 (N + 3 slots on each of 8 levels), so
+    7686 features fill the 16384 words exactly and run, bit-equal to the oracle; 7687 and 16000
+    (>= 131 KB) extract but do not match; the same two engines' successors at 1200 features then
+    match the oracle."""
+    cam = fc.CAMERAS["euroc"]
+    mb = fc.mb_of(cam.bf, cam.fx)
+    L, R = fc.wide_reference(oracle_mod, "euroc")[:2]
+    for nf in (7687, 16000):
+        exL, exR = amd.ORBextractor(nf), amd.ORBextractor(nf)
+        kL, _ = exL(L)
+        kR, _ = exR(R)
+        assert len(kL) > 1200 and len(kR) > 1200
+        assert 2 * (cam.h + 2) + 2 * _capacity(amd, exL) > 16384
+        with pytest.raises(amd.OrbslamError, match="status -1"):
+            amd.compute_stereo_matches(exL, exR, len(kL), cam.bf, mb)
+        exL.close()
+        exR.close()
+    for nf in (1200, 7686):
+        *ref, ((u_ref, d_ref),) = fc.stereo_reference(oracle_mod, L, R, nf, 20, 7, cam.bf, (mb,))
+        exL, exR, n = _drop_in(amd, L, R, nf, 20, 7, ref, f"nf {nf}")
+        if nf == 7686:
+            assert 2 * (cam.h + 2) + 2 * _capacity(amd, exL) == 16384
+        _assert_same_stereo(amd.compute_stereo_matches(exL, exR, n, cam.bf, mb), (u_ref, d_ref), f"nf {nf}")
