@@ -409,7 +409,14 @@ int orbt_search_by_sim3(orbt_engine *e, const orbt_frame *kf1, const int32_t *kf
 
 /* Batched device-resident form (throughput path): stage independent problems into slots
  * (host -> HBM), run one launch chain over all slots, fetch per slot. `last`, `last_mp`,
- * `last_outlier` may be NULL when only orbt_run_local_batch is used. */
+ * `last_outlier` may be NULL when only orbt_run_local_batch is used.
+ * cap_kp <= 8192 (keypoints of a frame and of its last frame / candidate keyframe): the grid sort, the
+ * per-slot claim arrays in LDS and the 16-bit keypoint index of a kept candidate are sized to that;
+ * a larger cap_kp -- also through a single-call entry with a larger frame -- returns ORBX_EINVAL before
+ * anything is launched. cap_mp has no such limit.
+ * A KeyFrame-side search (orbt_fuse_candidates, the *_sim3 entries) reads min_x .. max_y truncated to int,
+ * as KeyFrame::IsInImage / GetFeaturesInArea do with KeyFrame's `const int mnMinX ...`; the grid cells
+ * themselves are the Frame's (float bounds). */
 int orbt_reserve(orbt_engine *e, int n_slots, int cap_kp, int cap_mp);
 int orbt_stage(orbt_engine *e, int slot, const orbt_frame *F, const orbt_mappoints *M,
                const orbt_frame *last, const int32_t *last_mp, const uint8_t *last_outlier,
@@ -523,7 +530,10 @@ int orbb_search_by_bow_kf(orbb_engine *e, const orbb_keyframe *kf1, const orbb_k
 /* Batched device-resident form: stage (a, b) pairs into slots -- SearchByBoW reads a = KeyFrame,
  * b = Frame (or KeyFrame 2); SearchForTriangulation a = KF1, b = KF2 (F12 / Cw1 / T2w may be NULL
  * for SearchByBoW) -- run one launch chain over all slots, fetch per slot (tri = 0:
- * matches[b.n], tri = 1: pairs[2 * n], tri = 2: matches12[a.n] of orbb_run_bowkf_batch). */
+ * matches[b.n], tri = 1: pairs[2 * n], tri = 2: matches12[a.n] of orbb_run_bowkf_batch).
+ * cap_kp <= 4096 keypoints per keyframe (one FeatureVector node may hold all of them); a larger cap_kp --
+ * also through a single-call entry with a larger keyframe -- returns ORBX_EINVAL before anything is
+ * launched. */
 int orbb_reserve(orbb_engine *e, int n_slots, int cap_kp);
 int orbb_stage(orbb_engine *e, int slot, const orbb_keyframe *a, const orbb_keyframe *b, const float F12[9],
                const float Cw1[3], const float T2w[12]);

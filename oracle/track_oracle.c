@@ -127,6 +127,27 @@ static int frame_grid(const orbt_frame *F, orc_frame_grid *g) {
                           F->max_y);
 }
 
+/* A KeyFrame keeps the image bounds as int (KeyFrame.h:380-383 `const int mnMinX, mnMinY, mnMaxX, mnMaxY`,
+ * initialised from the Frame's floats at KeyFrame.cc:53-54), so KeyFrame::IsInImage (:841-844) and the
+ * window origin of KeyFrame::GetFeaturesInArea (:802-815) see them truncated toward zero. The grid itself
+ * (mGrid) and the cell size (mfGridElementWidthInv / HeightInv) are copied from the Frame and keep its
+ * float bounds. Only a distorted camera (fractional bounds) tells the two apart. */
+typedef struct { float min_x, max_x, min_y, max_y; } kf_bounds;
+static kf_bounds kf_int_bounds(const orbt_frame *F) {
+    const kf_bounds b = {(float)(int)F->min_x, (float)(int)F->max_x, (float)(int)F->min_y, (float)(int)F->max_y};
+    return b;
+}
+static int kf_is_in_image(const kf_bounds *b, float u, float v) {
+    return u >= b->min_x && u < b->max_x && v >= b->min_y && v < b->max_y;
+}
+static int kf_features_in_area(const orc_frame_grid *g, const kf_bounds *b, float x, float y, float r, int *out,
+                               int cap) {
+    orc_frame_grid k = *g;
+    k.minX = b->min_x;
+    k.minY = b->min_y;
+    return orc_features_in_area(&k, x, y, r, -1, -1, out, cap);
+}
+
 int orc_search_local_points(const orbt_frame *F, const orbt_mappoints *M, float viewCosLimit, float th,
                             float nnratio, const uint8_t *kp_blocked, orbt_view *view, int32_t *owner) {
     const int TH_HIGH = 100;
@@ -414,6 +435,7 @@ int orc_search_by_projection_sim3(const orbt_frame *kf, const float Scw[16], con
     orc_sim3_unscale(Scw, K.Tcw, K.Ow);
     orc_frame_grid g;
     frame_grid(&K, &g);
+    const kf_bounds kb = kf_int_bounds(&K);
     uint8_t *found = (uint8_t *)calloc((size_t)M->n + 1, 1);   /* spAlreadyFound */
     for (int i = 0; i < N; i++)
         if (matched[i] >= 0 && matched[i] < M->n) found[matched[i]] = 1;
@@ -428,7 +450,7 @@ int orc_search_by_projection_sim3(const orbt_frame *kf, const float Scw[16], con
         const float invz = 1 / p3Dc[2];
         const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
         const float u = K.fx * x + K.cx, v = K.fy * y + K.cy;
-        if (!(u >= K.min_x && u < K.max_x && v >= K.min_y && v < K.max_y)) continue;   /* KeyFrame::IsInImage */
+        if (!kf_is_in_image(&kb, u, v)) continue;                               /* KeyFrame::IsInImage */
         const float maxDistance = 1.2f * M->max_dist[m], minDistance = 0.8f * M->min_dist[m];
         const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
         double ss = 0;
@@ -444,7 +466,7 @@ int orc_search_by_projection_sim3(const orbt_frame *kf, const float Scw[16], con
         if (nPredictedLevel < 0) nPredictedLevel = 0;
         else if (nPredictedLevel >= K.nlevels) nPredictedLevel = K.nlevels - 1;
         const float radius = th * K.scale_factors[nPredictedLevel];
-        const int nc = orc_features_in_area(&g, u, v, radius, -1, -1, cand, N + 1);   /* KeyFrame version */
+        const int nc = kf_features_in_area(&g, &kb, u, v, radius, cand, N + 1);
         if (nc == 0) continue;
         const uint8_t *dMP = M->desc + 32 * (size_t)m;
         int bestDist = 256, bestIdx = -1;
@@ -477,6 +499,7 @@ void orc_fuse_sim3_candidates(const orbt_frame *kf, const float Scw[16], const o
     orc_sim3_unscale(Scw, K.Tcw, K.Ow);
     orc_frame_grid g;
     frame_grid(&K, &g);
+    const kf_bounds kb = kf_int_bounds(&K);
     int *cand = (int *)malloc(sizeof(int) * ((size_t)N + 1));
     for (int m = 0; m < M->n; m++) {
         best_idx[m] = -1;
@@ -489,7 +512,7 @@ void orc_fuse_sim3_candidates(const orbt_frame *kf, const float Scw[16], const o
         const float invz = (float)(1.0 / (double)p3Dc[2]);
         const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
         const float u = K.fx * x + K.cx, v = K.fy * y + K.cy;
-        if (!(u >= K.min_x && u < K.max_x && v >= K.min_y && v < K.max_y)) continue;
+        if (!kf_is_in_image(&kb, u, v)) continue;
         const float maxDistance = 1.2f * M->max_dist[m], minDistance = 0.8f * M->min_dist[m];
         const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
         double ss = 0;
@@ -504,7 +527,7 @@ void orc_fuse_sim3_candidates(const orbt_frame *kf, const float Scw[16], const o
         if (lvl < 0) lvl = 0;
         else if (lvl >= K.nlevels) lvl = K.nlevels - 1;
         const float radius = th * K.scale_factors[lvl];
-        const int nc = orc_features_in_area(&g, u, v, radius, -1, -1, cand, N + 1);
+        const int nc = kf_features_in_area(&g, &kb, u, v, radius, cand, N + 1);
         const uint8_t *dMP = M->desc + 32 * (size_t)m;
         int bestDist = INT_MAX, bestIdx = -1;
         for (int c = 0; c < nc; c++) {
@@ -529,6 +552,7 @@ static int sim3_pass(const orbt_frame *src, const int32_t *mp_src, const uint8_t
                      const orbt_frame *k1, const float sR[9], const float st[3], const orbt_mappoints *M, float th,
                      orc_frame_grid *g, int *cand, int *vnMatch) {
     const int TH_HIGH = 100;
+    const kf_bounds kb = kf_int_bounds(dst);
     float T[12];
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) T[4 * r + c] = sR[3 * r + c];
@@ -547,7 +571,7 @@ static int sim3_pass(const orbt_frame *src, const int32_t *mp_src, const uint8_t
         const float invz = (float)(1.0 / (double)pc2[2]);
         const float x = pc2[0] * invz, y = pc2[1] * invz;
         const float u = k1->fx * x + k1->cx, v = k1->fy * y + k1->cy;
-        if (!(u >= dst->min_x && u < dst->max_x && v >= dst->min_y && v < dst->max_y)) continue;
+        if (!kf_is_in_image(&kb, u, v)) continue;                                /* pKF2->IsInImage */
         const float maxDistance = 1.2f * M->max_dist[m], minDistance = 0.8f * M->min_dist[m];
         double ss = 0;
         for (int k = 0; k < 3; k++) { const double t = pc2[k]; ss += t * t; }
@@ -557,7 +581,7 @@ static int sim3_pass(const orbt_frame *src, const int32_t *mp_src, const uint8_t
         if (lvl < 0) lvl = 0;
         else if (lvl >= dst->nlevels) lvl = dst->nlevels - 1;
         const float radius = th * dst->scale_factors[lvl];
-        const int nc = orc_features_in_area(g, u, v, radius, -1, -1, cand, dst->n + 1);
+        const int nc = kf_features_in_area(g, &kb, u, v, radius, cand, dst->n + 1);
         const uint8_t *dMP = M->desc + 32 * (size_t)m;
         int bestDist = INT_MAX, bestIdx = -1;
         for (int c = 0; c < nc; c++) {
@@ -839,6 +863,7 @@ void orc_fuse_candidates(const orbt_frame *kf, const orbt_mappoints *M, float th
                          int32_t *best_dist) {
     orc_frame_grid g;
     frame_grid(kf, &g);
+    const kf_bounds kb = kf_int_bounds(kf);
     int *cand = (int *)malloc(sizeof(int) * ((size_t)kf->n + 1));
     for (int i = 0; i < M->n; i++) {
         best_idx[i] = -1;
@@ -851,7 +876,7 @@ void orc_fuse_candidates(const orbt_frame *kf, const orbt_mappoints *M, float th
         const float invz = 1 / p3Dc[2];
         const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
         const float u = kf->fx * x + kf->cx, v = kf->fy * y + kf->cy;
-        if (!(u >= kf->min_x && u < kf->max_x && v >= kf->min_y && v < kf->max_y)) continue;   /* IsInImage */
+        if (!kf_is_in_image(&kb, u, v)) continue;                        /* IsInImage */
         const float ur = u - kf->mbf * invz;
         const float maxDistance = 1.2f * M->max_dist[i], minDistance = 0.8f * M->min_dist[i];
         const float PO[3] = {P[0] - kf->Ow[0], P[1] - kf->Ow[1], P[2] - kf->Ow[2]};
@@ -868,7 +893,7 @@ void orc_fuse_candidates(const orbt_frame *kf, const orbt_mappoints *M, float th
         if (nPredictedLevel < 0) nPredictedLevel = 0;
         else if (nPredictedLevel >= kf->nlevels) nPredictedLevel = kf->nlevels - 1;
         const float radius = th * kf->scale_factors[nPredictedLevel];
-        const int nc = orc_features_in_area(&g, u, v, radius, -1, -1, cand, kf->n + 1);
+        const int nc = kf_features_in_area(&g, &kb, u, v, radius, cand, kf->n + 1);
         const uint8_t *dMP = M->desc + 32 * (size_t)i;
         int bestDist = 256, bestIdx = -1;
         for (int c = 0; c < nc; c++) {

@@ -63,6 +63,10 @@ struct FrameDev {
     float Ow[3];
     float fx, fy, cx, cy, mbf, mb;
     float min_x, max_x, min_y, max_y, inv_w, inv_h;
+    // the same bounds as a KeyFrame holds them: `const int mnMinX, ...` (KeyFrame.h:380-383), truncated
+    // toward zero from the Frame's floats (KeyFrame.cc:53-54). KeyFrame::IsInImage and the window origin
+    // of KeyFrame::GetFeaturesInArea read these; the grid and inv_w / inv_h stay the Frame's
+    float kf_min_x, kf_max_x, kf_min_y, kf_max_y;
     int nlevels;
     float log_scale;
     float scale[16];
@@ -199,31 +203,39 @@ __device__ inline bool examined_conflict(const Cand &c, int last_ex, const int *
     return conflict;
 }
 
-// Frame::GetFeaturesInArea (Frame.cc:590-671) window: returns false if empty.
+// Frame::GetFeaturesInArea (Frame.cc:590-671) window: returns false if empty. kKF: the KeyFrame
+// form (KeyFrame.cc:794-817), whose origin is the int-truncated mnMinX / mnMinY.
+template <bool kKF = false>
 __device__ inline bool grid_window(const FrameDev &f, float x, float y, float r, int &x0, int &x1, int &y0,
                                    int &y1) {
-    x0 = max(0, (int)floorf((x - f.min_x - r) * f.inv_w));
+    const float ox = kKF ? f.kf_min_x : f.min_x, oy = kKF ? f.kf_min_y : f.min_y;
+    x0 = max(0, (int)floorf((x - ox - r) * f.inv_w));
     if (x0 >= GRID_COLS) return false;
-    x1 = min(GRID_COLS - 1, (int)ceilf((x - f.min_x + r) * f.inv_w));
+    x1 = min(GRID_COLS - 1, (int)ceilf((x - ox + r) * f.inv_w));
     if (x1 < 0) return false;
-    y0 = max(0, (int)floorf((y - f.min_y - r) * f.inv_h));
+    y0 = max(0, (int)floorf((y - oy - r) * f.inv_h));
     if (y0 >= GRID_ROWS) return false;
-    y1 = min(GRID_ROWS - 1, (int)ceilf((y - f.min_y + r) * f.inv_h));
+    y1 = min(GRID_ROWS - 1, (int)ceilf((y - oy + r) * f.inv_h));
     if (y1 < 0) return false;
     return true;
+}
+
+// KeyFrame::IsInImage (KeyFrame.cc:841-844) on the int bounds
+__device__ inline bool kf_is_in_image(const FrameDev &f, float u, float v) {
+    return u >= f.kf_min_x && u < f.kf_max_x && v >= f.kf_min_y && v < f.kf_max_y;
 }
 
 // Scan the window in the reference's candidate order (ix, iy, insertion order) applying the
 // static filters; `claimed` (may be null) adds the dynamic claim filter (rescan fallback).
 // Returns the number of candidates that passed; keeps the K smallest (dist, position) keys.
-template <bool kLocal>
+template <bool kLocal, bool kKF = false>
 __device__ int scan_window(const Slots &S, int s, const FrameDev &f, float x, float y, float r, int minL,
                            int maxL, const uint8_t *qdesc, float xr, float er_r, const uint8_t *claimed,
                            float last_angle, Cand &c) {
 #pragma unroll
     for (int k = 0; k < TOPK; k++) { c.key[k] = 0xFFFFFFFFu; c.idx[k] = 0; c.oct[k] = -1; c.bin[k] = -1; }
     int cx0, cx1, cy0, cy1;
-    if (!grid_window(f, x, y, r, cx0, cx1, cy0, cy1)) return 0;
+    if (!grid_window<kKF>(f, x, y, r, cx0, cx1, cy0, cy1)) return 0;
     const bool bCheckLevels = (minL > 0) || (maxL >= 0);
     const float4 *rec = S.grec + (long long)s * S.sort_cap;
     const int *cs = S.cell_start + (long long)s * (NCELL + 1);
@@ -545,7 +557,7 @@ __device__ int sim3_query(const Slots &S, int s, const FrameDev &f, int m, float
     const float invz = 1 / p3Dc[2];
     const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
     const float u = f.fx * x + f.cx, v = f.fy * y + f.cy;
-    if (!(u >= f.min_x && u < f.max_x && v >= f.min_y && v < f.max_y)) return 0;   // KeyFrame::IsInImage
+    if (!kf_is_in_image(f, u, v)) return 0;
     const float maxDistance = 1.2f * S.maxd[mb], minDistance = 0.8f * S.mind[mb];
     const float PO[3] = {P[0] - f.Ow[0], P[1] - f.Ow[1], P[2] - f.Ow[2]};
     double ss = 0;
@@ -560,7 +572,8 @@ __device__ int sim3_query(const Slots &S, int s, const FrameDev &f, int m, float
     if (lvl < 0) lvl = 0;
     else if (lvl >= f.nlevels) lvl = f.nlevels - 1;
     const float radius = th * f.scale[lvl];
-    return scan_window<false>(S, s, f, u, v, radius, lvl - 1, lvl, S.mdesc + mb * 32, 0.f, INFINITY, claimed, 0.f, c);
+    return scan_window<false, true>(S, s, f, u, v, radius, lvl - 1, lvl, S.mdesc + mb * 32, 0.f, INFINITY, claimed, 0.f,
+                                    c);
 }
 
 // ---- SearchByProjection(CurrentFrame, LastFrame) query of last keypoint i (ORBmatcher.cc:1786-1870);
@@ -765,7 +778,7 @@ __global__ __launch_bounds__(256) void track_fuse_kernel(Slots S, float th, int 
             const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
             u = f.fx * x + f.cx;
             v = f.fy * y + f.cy;
-            ok = u >= f.min_x && u < f.max_x && v >= f.min_y && v < f.max_y;   // KeyFrame::IsInImage
+            ok = kf_is_in_image(f, u, v);
             ur = u - f.mbf * invz;
         }
         if (ok) {
@@ -790,7 +803,7 @@ __global__ __launch_bounds__(256) void track_fuse_kernel(Slots S, float th, int 
         }
         int cx0, cx1, cy0, cy1;
         const float radius = th * f.scale[lvl];
-        if (ok && grid_window(f, u, v, radius, cx0, cx1, cy0, cy1)) {
+        if (ok && grid_window<true>(f, u, v, radius, cx0, cx1, cy0, cy1)) {
             const float4 *rec = S.grec + (long long)s * S.sort_cap;
             const int *cs = S.cell_start + (long long)s * (NCELL + 1);
             const long long kb = (long long)s * S.cap_kp;
@@ -848,7 +861,7 @@ __global__ __launch_bounds__(256) void track_sim3_match_kernel(Slots S, float th
                 const float x = pc2[0] * invz, y = pc2[1] * invz;
                 u = f.pfx * x + f.pcx;
                 v = f.pfy * y + f.pcy;
-                ok = u >= f.min_x && u < f.max_x && v >= f.min_y && v < f.max_y;   // KeyFrame::IsInImage
+                ok = kf_is_in_image(f, u, v);
             }
             if (ok) {
                 double ss = 0;
@@ -864,7 +877,7 @@ __global__ __launch_bounds__(256) void track_sim3_match_kernel(Slots S, float th
                 else if (lvl >= f.nlevels) lvl = f.nlevels - 1;
             }
             const float radius = th * f.scale[lvl];
-            if (ok && grid_window(f, u, v, radius, cx0, cx1, cy0, cy1)) {
+            if (ok && grid_window<true>(f, u, v, radius, cx0, cx1, cy0, cy1)) {
                 const float4 *rec = S.grec + (long long)s * S.sort_cap;
                 const int *cs = S.cell_start + (long long)s * (NCELL + 1);
                 const long long kb = (long long)s * S.cap_kp;
@@ -969,6 +982,8 @@ void fill_frame(FrameDev &d, const orbt_frame *F) {
     // Frame.cc:183-184 (static_cast<float>(FRAME_GRID_COLS) / static_cast<float>(mnMaxX - mnMinX))
     d.inv_w = (float)GRID_COLS / (F->max_x - F->min_x);
     d.inv_h = (float)GRID_ROWS / (F->max_y - F->min_y);
+    d.kf_min_x = (float)(int)F->min_x; d.kf_max_x = (float)(int)F->max_x;
+    d.kf_min_y = (float)(int)F->min_y; d.kf_max_y = (float)(int)F->max_y;
     d.nlevels = F->nlevels;
     d.log_scale = F->log_scale_factor;
     std::memcpy(d.scale, F->scale_factors, sizeof d.scale);

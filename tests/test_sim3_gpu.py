@@ -85,3 +85,93 @@ def test_search_by_sim3_batched(amd, oracle_mod):
         nf_r, m_r = oracle_mod.search_by_sim3(p, 7.5)
         assert nf == nf_r
         np.testing.assert_array_equal(m, m_r)
+
+
+# ---- hand-built cases of matcher_cases.py (tests/test_matcher_cases_cpu.py shows what each one reaches)
+def _cmp_sim3_modes(t, oracle_mod, p):
+    for th in (10, 4):
+        nm_r, m_r = oracle_mod.search_by_projection_sim3(p, th)
+        nm_g, m_g = t.search_by_projection_sim3(p, th)
+        assert nm_g == nm_r
+        np.testing.assert_array_equal(m_g, m_r)
+    bi_r, bd_r = oracle_mod.fuse_sim3_candidates(p, 4.0)
+    bi_g, bd_g = t.fuse_sim3_candidates(p, 4.0)
+    np.testing.assert_array_equal(bi_g, bi_r)
+    np.testing.assert_array_equal(bd_g, bd_r)
+
+
+def _track_case_names():
+    import matcher_cases as mc
+    return list(mc.TRACK_CASES)
+
+
+@pytest.mark.parametrize("name", _track_case_names())
+def test_matcher_cases_sim3(amd, oracle_mod, name):
+    """The loop-closing projection search (every claim blocks, TH_LOW) and Fuse(pKF, Scw) on the crowds, the
+    decisions at equality, the quantised problems and the capacity cases."""
+    import matcher_cases as mc
+    t = amd.Tracker()
+    _cmp_sim3_modes(t, oracle_mod, mc.track_case(name))
+    t.close()
+
+
+def _camera_names():
+    import matcher_cases as mc
+    return list(mc.CAMERAS)
+
+
+@pytest.mark.parametrize("name", _camera_names())
+def test_image_bounds_sim3(amd, oracle_mod, name):
+    """KeyFrame::IsInImage / GetFeaturesInArea with the int-truncated bounds of a KeyFrame at fractional, non-zero
+    and negative image bounds: Sim3 projection, Fuse(pKF, Scw) and SearchBySim3."""
+    import matcher_cases as mc
+    t = amd.Tracker()
+    _cmp_sim3_modes(t, oracle_mod, mc.bounds_case(oracle_mod, name))
+    _cmp_sim3_modes(t, oracle_mod, mc.bounds_case(oracle_mod, name, "reloc"))
+    p = mc.bounds_case(oracle_mod, name, "pair")
+    for th in (7.5, 4.0):
+        nf_r, m_r = oracle_mod.search_by_sim3(p, th)
+        nf_g, m_g = t.search_by_sim3(p, th)
+        assert nf_g == nf_r
+        np.testing.assert_array_equal(m_g, m_r)
+    t.close()
+
+
+@pytest.mark.parametrize("name", ["gates", "ties", "quant2", "cap8192"])
+def test_matcher_cases_search_by_sim3(amd, oracle_mod, name):
+    import matcher_cases as mc
+    p = mc.pair_case(name)
+    t = amd.Tracker()
+    nf_r, m_r = oracle_mod.search_by_sim3(p, 7.5)
+    nf_g, m_g = t.search_by_sim3(p, 7.5)
+    assert nf_g == nf_r
+    np.testing.assert_array_equal(m_g, m_r)
+    t.close()
+
+
+def test_matcher_cases_sim3_batched(amd, oracle_mod):
+    """Crowds and bounds cases of different sizes in one batch (projection search), and the bounds pairs in one
+    SearchBySim3 batch."""
+    import matcher_cases as mc
+    probs = [mc.track_case("crowd_" + n) for n in mc.CROWDS] + [mc.bounds_case(oracle_mod, n) for n in mc.CAMERAS]
+    t = amd.Tracker()
+    t.reserve(len(probs), max(len(p["frame"]["keys_un"]) for p in probs), max(len(p["map"]["Xw"]) for p in probs))
+    for s, p in enumerate(probs):
+        t.stage_sim3(s, p)
+    t.run_sim3_batch(len(probs), 10)
+    for s, p in enumerate(probs):
+        nm, m = t.fetch_sim3(s, p)
+        nm_r, m_r = oracle_mod.search_by_projection_sim3(p, 10)
+        assert nm == nm_r, s
+        np.testing.assert_array_equal(m, m_r)
+    pairs = [mc.bounds_case(oracle_mod, n, "pair") for n in mc.CAMERAS] + [mc.pair_case("gates")]
+    t.reserve(2 * len(pairs), 900, 800)
+    for k, p in enumerate(pairs):
+        t.stage_search_by_sim3(k, p)
+    t.run_sim3_match_batch(len(pairs), 7.5)
+    for k, p in enumerate(pairs):
+        nf, m = t.fetch_search_by_sim3(k, p)
+        nf_r, m_r = oracle_mod.search_by_sim3(p, 7.5)
+        assert nf == nf_r, k
+        np.testing.assert_array_equal(m, m_r)
+    t.close()

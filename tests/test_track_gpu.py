@@ -160,3 +160,90 @@ def test_fuse_batched(amd, oracle_mod):
         bi_r, bd_r = oracle_mod.fuse_candidates(p, 3.0)
         assert np.array_equal(bi, bi_r) and np.array_equal(bd, bd_r)
     t.close()
+
+
+# ---- hand-built cases of matcher_cases.py (tests/test_matcher_cases_cpu.py shows what each one reaches)
+def _cmp_track_modes(t, oracle_mod, p, reloc=None, nnratio=0.8):
+    """local, frame (with and without the rotation check), relocalisation (ORBdist 100 and 64) and Fuse."""
+    nm_r, own_r, view_r = oracle_mod.search_local_points(p, nnratio=nnratio)
+    nm_g, own_g, view_g = t.search_local_points(p, nnratio=nnratio)
+    _cmp_view(view_g, view_r)
+    assert nm_g == nm_r and np.array_equal(own_g, own_r)
+    for ori in (True, False):
+        nm_r, own_r = oracle_mod.search_by_projection_frame(p, check_ori=ori)
+        nm_g, own_g = t.search_by_projection_frame(p, check_ori=ori)
+        assert nm_g == nm_r and np.array_equal(own_g, own_r)
+    q = p if reloc is None else reloc
+    for od, ori in ((100, True), (64, False)):
+        nm_r, own_r = oracle_mod.search_by_projection_keyframe(q, orb_dist=od, check_ori=ori)
+        nm_g, own_g = t.search_by_projection_keyframe(q, orb_dist=od, check_ori=ori)
+        assert nm_g == nm_r and np.array_equal(own_g, own_r)
+    bi_r, bd_r = oracle_mod.fuse_candidates(p, 3.0)
+    bi_g, bd_g = t.fuse_candidates(p, 3.0)
+    assert np.array_equal(bi_g, bi_r) and np.array_equal(bd_g, bd_r)
+
+
+def _track_case_names():
+    import matcher_cases as mc
+    return list(mc.TRACK_CASES)
+
+
+@pytest.mark.parametrize("name", _track_case_names())
+def test_matcher_cases(tracker, oracle_mod, name):
+    """Crowds across the 64-query windows, decisions at a gate / float equality / a tie, rotation bins on their
+    edges, PredictScale on an integer, quantised descriptors, and the capacity of 8192 keypoints."""
+    import matcher_cases as mc
+    p = mc.track_case(name)
+    for nnratio in ([r for r, _, _ in mc.RATIOS] if name == "ratio" else [0.8]):
+        _cmp_track_modes(tracker, oracle_mod, p, nnratio=nnratio)
+
+
+def _camera_names():
+    import matcher_cases as mc
+    return list(mc.CAMERAS)
+
+
+@pytest.mark.parametrize("name", _camera_names())
+def test_image_bounds(tracker, oracle_mod, name):
+    """Fractional, non-zero and negative image bounds at 640x480, 752x480 and 1280x720, keypoints on the bounds and
+    on cell boundaries, projections exactly on a bound, camera z == 0."""
+    import matcher_cases as mc
+    _cmp_track_modes(tracker, oracle_mod, mc.bounds_case(oracle_mod, name),
+                     reloc=mc.bounds_case(oracle_mod, name, "reloc"))
+
+
+def test_matcher_cases_batched(amd, oracle_mod):
+    """Crowds, bounds and equality cases of different sizes in one batch, through every batched entry."""
+    import matcher_cases as mc
+    t = amd.Tracker()
+    with pytest.raises(amd.OrbslamError):
+        t.reserve(1, 8193, 100)
+    probs = [mc.track_case("crowd_" + n) for n in mc.CROWDS]
+    probs += [mc.bounds_case(oracle_mod, n, k) for n in mc.CAMERAS for k in ("track", "reloc")]
+    probs += [mc.track_case(n) for n in ("gates", "ties", "rot_edges", "rot_ten_percent", "scale", "quant1")]
+    cap_kp = max(max(len(p["frame"]["keys_un"]), len(p["last"]["keys_un"])) for p in probs)
+    t.reserve(len(probs), cap_kp, max(len(p["map"]["Xw"]) for p in probs))
+    for s, p in enumerate(probs):
+        t.stage(s, p)
+    t.run_local_batch(len(probs), th=1.0, nnratio=0.8)
+    for s, p in enumerate(probs):
+        nm, own, view = t.fetch(s, len(p["frame"]["keys_un"]), len(p["map"]["Xw"]))
+        nm_r, own_r, view_r = oracle_mod.search_local_points(p, th=1.0, nnratio=0.8)
+        assert nm == nm_r and np.array_equal(own, own_r), s
+        _cmp_view(view, view_r)
+    t.run_frame_batch(len(probs), th=15.0)
+    for s, p in enumerate(probs):
+        nm, own, _ = t.fetch(s, len(p["frame"]["keys_un"]))
+        nm_r, own_r = oracle_mod.search_by_projection_frame(p, th=15.0)
+        assert nm == nm_r and np.array_equal(own, own_r), s
+    t.run_reloc_batch(len(probs), th=10.0, orb_dist=100)
+    for s, p in enumerate(probs):
+        nm, own, _ = t.fetch(s, len(p["frame"]["keys_un"]))
+        nm_r, own_r = oracle_mod.search_by_projection_keyframe(p, th=10.0, orb_dist=100)
+        assert nm == nm_r and np.array_equal(own, own_r), s
+    t.run_fuse_batch(len(probs), 3.0)
+    for s, p in enumerate(probs):
+        bi, bd = t.fetch_fuse(s, len(p["map"]["Xw"]))
+        bi_r, bd_r = oracle_mod.fuse_candidates(p, 3.0)
+        assert np.array_equal(bi, bi_r) and np.array_equal(bd, bd_r), s
+    t.close()
