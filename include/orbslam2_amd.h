@@ -732,6 +732,100 @@ int orbo_stage(orbo_engine *e, int slot, const orbo_problem *p);
 int orbo_run_batch(orbo_engine *e, int n_slots, void *stream);
 int orbo_fetch(orbo_engine *e, int slot, orbo_result *r);
 
+/* -------- KeyFrameDatabase (the loop and relocalisation queries in front of ComputeSim3 / Relocalization) -------- */
+
+#define ORBD_LOOP 0              /* KeyFrameDatabase::DetectLoopCandidates */
+#define ORBD_RELOC 1             /* KeyFrameDatabase::DetectRelocalizationCandidates */
+#define ORBD_L1_NORM 0           /* DBoW2 ScoringType L1_NORM: the only scoring supported (ORBvoc.txt's) */
+#define ORBD_MAX_WORDS 4096      /* words of one BowVector (orbv_transform's feature limit) */
+#define ORBD_MAX_COVISIBLES 10   /* GetBestCovisibilityKeyFrames(10) (KeyFrameDatabase.cc:212, :355) */
+
+/* One query. words / values: the BowVector (pKF->mBowVec / F->mBowVec), n <= ORBD_MAX_WORDS, words strictly
+ * ascending and < n_words, values finite. ORBD_LOOP also reads connected[n_connected] =
+ * pKF->GetConnectedKeyFrames() as ids (ids that are not in the database are ignored) and min_score;
+ * ORBD_RELOC ignores both. Host pointers. */
+typedef struct {
+    int32_t kind;
+    int32_t n;
+    const uint32_t *words;
+    const double *values;
+    const int64_t *connected;
+    int32_t n_connected;
+    float min_score;
+} orbd_query;
+
+/* Caller-allocated; every array holds `cap` entries, the lists after `candidates` may each be NULL.
+ * ORBX_ECAP (with the counts filled in) when n_candidates > cap, or n_scored > cap with a list wanted;
+ * cap = orbd_size always suffices. */
+typedef struct {
+    int32_t cap;
+    int32_t n_candidates;
+    int64_t *candidates;         /* vpLoopCandidates / vpRelocCandidates (:245-263, :399-417), in order */
+    int32_t n_scored;
+    int64_t *scored_ids;         /* lScoreAndMatch (:162-196, :323-340) in list order: keyframe, */
+    float *scored_si;            /*   si, */
+    int32_t *scored_words;       /*   mnLoopWords / mnRelocWords */
+    float *acc_score;            /* lAccScoreAndMatch (:203-238, :345-390): accScore and */
+    int64_t *acc_best;           /*   pBestKF of the group of scored_ids[i] */
+    int32_t max_common_words;    /* maxCommonWords (:166-171); 0 = lKFsSharingWords was empty */
+    int32_t min_common_words;    /* minCommonWords = (int)(maxCommonWords * 0.8f) (:174) */
+} orbd_result;
+
+typedef struct orbd_db orbd_db;
+
+/* KeyFrameDatabase::KeyFrameDatabase(voc) (KeyFrameDatabase.cc:45-50): n_words = voc.size(). scoring is the
+ * vocabulary's ScoringType; anything but ORBD_L1_NORM is ORBX_EINVAL. As orbs_*: a host object until a
+ * call whose arguments passed every check needs the device -- orbd_create / orbd_reserve succeed without a
+ * GPU and every ORBX_EINVAL below is returned before the device is touched. All entries serialise on an
+ * internal mutex, as the reference's mMutex does. */
+int orbd_create(int n_words, int scoring, orbd_db **out);
+void orbd_destroy(orbd_db *db);
+/* KeyFrameDatabase::add (:57-65): the keyframe's BowVector goes to HBM (storage grows by
+ * reallocate-and-copy). ORBX_EINVAL: NULL pointers, n outside 0..ORBD_MAX_WORDS, words not strictly
+ * ascending or >= n_words, kf_id negative or already in the database. */
+int orbd_add(orbd_db *db, int64_t kf_id, const uint32_t *words, const double *values, int n);
+/* The same, device to device, from frame `frame` of the vocabulary's last orbv_transform_batch_device;
+ * only the BowVector's length (4 bytes) comes back to the host. ORBX_EINVAL also for a frame that batch
+ * did not hold or a vocabulary with more words than n_words. */
+int orbd_add_from_vocab(orbd_db *db, int64_t kf_id, orbv_vocab *v, int frame);
+/* KeyFrameDatabase::erase (:72-94); ORBX_EINVAL for an id that is not in the database. An erased id may
+ * be added again: it then stands at the back of every inverted list, as in the reference. */
+int orbd_erase(orbd_db *db, int64_t kf_id);
+/* KeyFrameDatabase::clear (:97-101) */
+int orbd_clear(orbd_db *db);
+int orbd_size(orbd_db *db, int32_t *n);
+/* mvpOrderedConnectedKeyFrames[0 .. n) of a keyframe in the database, n <= ORBD_MAX_COVISIBLES (else
+ * ORBX_EINVAL): what GetBestCovisibilityKeyFrames(10) returns to the group walk (:212, :355). Empty until
+ * set, and again after erase + add. An id that is not in the database when a query runs is skipped. */
+int orbd_set_covisibles(orbd_db *db, int64_t kf_id, const int64_t *ids, int n);
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (:113-264) or DetectRelocalizationCandidates(F)
+ * (:275-418) for one query, every call a fresh query id (the reference's behaviour for a repeated mnId is
+ * not reproduced). The reference reads mRelocScore (:374) of any neighbour sharing a word, also one that
+ * failed the word threshold in this query and so kept the value of an earlier query; that state lives in
+ * the database, survives between queries, and starts at 0.0f on add (the reference leaves it
+ * uninitialised). */
+int orbd_detect(orbd_db *db, const orbd_query *query, orbd_result *result);
+/* Batch form: n_slots staged queries give the results of orbd_detect issued one after another in slot
+ * order (the mRelocScore state included). orbd_run_batch enqueues the kernels and the copy of every slot's
+ * results to page-locked host memory on `stream` (hipStream_t; NULL = the database's own) and returns; the
+ * one host synchronisation of the batch is made by whichever orbd_* call on this database comes next, and
+ * orbd_fetch then copies from host memory. orbd_stage_from_vocab takes the BowVector from the vocabulary's
+ * last batch, device to device, and kind / connected / min_score from `query` (its words / values / n are
+ * not read). ORBX_EINVAL: a slot out of range; ORBX_ESTATE: running a slot that was not staged, fetching
+ * a slot the last run did not cover. */
+int orbd_reserve(orbd_db *db, int n_slots);
+int orbd_stage(orbd_db *db, int slot, const orbd_query *query);
+int orbd_stage_from_vocab(orbd_db *db, int slot, const orbd_query *query, orbv_vocab *v, int frame);
+int orbd_run_batch(orbd_db *db, int n_slots, void *stream);
+int orbd_fetch(orbd_db *db, int slot, orbd_result *result);
+/* The covisible scan of LoopClosing::DetectLoop (LoopClosing.cc:163-184): scores[i] =
+ * (float)mpORBVocabulary->score(query, keyframe kf_ids[i]) -- L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), a double sum over the common words in ascending order
+ * -- and *min_score = the smallest of them, starting at 1. An id that is not in the database is skipped as
+ * a keyframe with isBad() is (:170): its scores[i] is -1. */
+int orbd_scores(orbd_db *db, const uint32_t *words, const double *values, int n, const int64_t *kf_ids, int n_ids,
+                float *scores, float *min_score);
+
 /* -------- local bundle adjustment (replaces Optimizer::LocalBundleAdjustment) -------- */
 
 /* The graph Optimizer::LocalBundleAdjustment (Optimizer.cc:646-898) builds from the map,

@@ -272,6 +272,18 @@ int launch(orbv_vocab *v, const uint8_t *d_desc, const int32_t *d_counts, int n_
 
 }  // namespace
 
+int orbamd::bow_batch_view(orbv_vocab *v, int frame, BowBatchView *out) {
+    if (!v || !out || frame < 0 || frame >= v->frames || !v->done_stream) return -1;
+    const size_t o = (size_t)frame * (size_t)v->cap;
+    out->words = v->o_words.as<uint32_t>() + o;
+    out->values = v->o_values.as<double>() + o;
+    out->n_words = v->o_nw.as<int>() + frame;
+    out->cap = v->cap;
+    out->voc_words = v->n_words;
+    out->done = v->done;
+    return 0;
+}
+
 extern "C" {
 
 int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent, const uint8_t *is_leaf,

@@ -160,6 +160,21 @@ inline hipEvent_t make_done_event() {
 }  // namespace orbamd
 
 struct orbf_state;   // per-engine Frame buffers (orb_frame.hip)
+struct orbv_vocab;   // orb_bow.hip
+
+namespace orbamd {
+// Frame `frame` of a vocabulary's last orbv_transform_batch_device, as the KeyFrameDatabase reads it in
+// place (orb_kfdb.hip): device pointers to its BowVector, the event recorded after the transform.
+struct BowBatchView {
+    const uint32_t *words;
+    const double *values;
+    const int *n_words;   // one int, on the device
+    int cap;              // entries per frame of words / values
+    int voc_words;        // words of the vocabulary
+    hipEvent_t done;
+};
+int bow_batch_view(orbv_vocab *v, int frame, BowBatchView *out);   // nonzero: no such frame
+}  // namespace orbamd
 
 struct orbx_engine {
     orbx_params p{};

@@ -13,15 +13,19 @@
 //   orbslam2_amd::ORBVocabulary                    <- DBoW2 TemplatedVocabulary<FORB>:
 //                                                     loadFromTextFile + transform (ComputeBoW)
 //   orbslam2_amd::Sim3Solver                        <- ORB_SLAM2::Sim3Solver (include/Sim3Solver.h:40-170)
+//   orbslam2_amd::KeyFrameDatabase                  <- ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h)
+//   orbslam2_amd::LoopClosing::DetectLoop           <- LoopClosing.cc:137-285 (host logic over the database)
 //
 // Error behaviour: the reference has no error path (it asserts / returns silently); a GPU
 // failure here throws std::runtime_error -- there is no CPU fallback.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -840,5 +844,184 @@ inline int Optimizer::OptimizeSim3(const Sim3KeyFrame &pKF1, const Sim3KeyFrame 
     g2oS12 = vS[0];
     return vn[0];
 }
+
+// ---- KeyFrameDatabase (orbd_*) and LoopClosing::DetectLoop -------------------------------------------------
+
+// What KeyFrameDatabase and LoopClosing::DetectLoop read of a KeyFrame. Keyframes are named by mnId.
+struct KeyFrameView {
+    int64_t mnId = 0;
+    BowVector mBowVec;
+    std::vector<int64_t> connected;    // GetConnectedKeyFrames(): every keyframe sharing a map point
+    std::vector<int64_t> covisibles;   // GetVectorCovisibleKeyFrames(): mvpOrderedConnectedKeyFrames without the bad
+                                       // ones; its first 10 are GetBestCovisibilityKeyFrames(10)
+};
+
+struct FrameView {                     // what DetectRelocalizationCandidates reads of a Frame
+    BowVector mBowVec;
+};
+
+class KeyFrameDatabase {
+public:
+    // KeyFrameDatabase(const ORBVocabulary &voc): one inverted list per word (KeyFrameDatabase.cc:45-50)
+    explicit KeyFrameDatabase(const ORBVocabulary &voc) : KeyFrameDatabase(voc.size()) {}
+    explicit KeyFrameDatabase(size_t n_words) { check(orbd_create((int)n_words, ORBD_L1_NORM, &h_), "orbd_create"); }
+    ~KeyFrameDatabase() { orbd_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+
+    // add(pKF): the BowVector goes to HBM with the keyframe's 10 best covisibles (the group walk of both
+    // queries reads pKFi->GetBestCovisibilityKeyFrames(10) of database keyframes)
+    void add(const KeyFrameView &kf) {
+        flatten(kf.mBowVec);
+        check(orbd_add(h_, kf.mnId, w_.data(), v_.data(), (int)w_.size()), "orbd_add");
+        SetCovisibles(kf.mnId, kf.covisibles);
+    }
+    // the covisibility graph changed (KeyFrame::UpdateConnections / UpdateBestCovisibles) for a stored keyframe
+    void SetCovisibles(int64_t mnId, const std::vector<int64_t> &ordered) {
+        const int n = (int)std::min<size_t>(ordered.size(), ORBD_MAX_COVISIBLES);
+        check(orbd_set_covisibles(h_, mnId, ordered.data(), n), "orbd_set_covisibles");
+    }
+    void erase(int64_t mnId) { check(orbd_erase(h_, mnId), "orbd_erase"); }
+    void clear() { check(orbd_clear(h_), "orbd_clear"); }
+    size_t size() const {
+        int32_t n = 0;
+        check(orbd_size(h_, &n), "orbd_size");
+        return (size_t)n;
+    }
+
+    // vector<KeyFrame*> DetectLoopCandidates(KeyFrame *pKF, float minScore) (KeyFrameDatabase.cc:113-264)
+    std::vector<int64_t> DetectLoopCandidates(const KeyFrameView &kf, float minScore) {
+        return detect(ORBD_LOOP, kf.mBowVec, &kf.connected, minScore);
+    }
+    // vector<KeyFrame*> DetectRelocalizationCandidates(Frame *F) (:275-418)
+    std::vector<int64_t> DetectRelocalizationCandidates(const FrameView &F) { return detect(ORBD_RELOC, F.mBowVec, nullptr, 0.0f); }
+    // The covisible scan of LoopClosing::DetectLoop (LoopClosing.cc:163-184): the smallest
+    // mpORBVocabulary->score(bow, keyframe) over `ids`, starting at 1; keyframes that are not in the database
+    // (bad ones were erased) are skipped. scores (may be NULL) gets one float per id, -1 = skipped.
+    float Scores(const BowVector &bow, const std::vector<int64_t> &ids, std::vector<float> *scores = nullptr) {
+        flatten(bow);
+        std::vector<float> sc(ids.size() + 1);
+        float min_score = 1.0f;
+        check(orbd_scores(h_, w_.data(), v_.data(), (int)w_.size(), ids.data(), (int)ids.size(), sc.data(), &min_score),
+              "orbd_scores");
+        sc.resize(ids.size());
+        if (scores) *scores = sc;
+        return min_score;
+    }
+    orbd_db *handle() { return h_; }
+
+private:
+    void flatten(const BowVector &b) {
+        w_.clear();
+        v_.clear();
+        for (const auto &e : b) {
+            w_.push_back(e.first);
+            v_.push_back(e.second);
+        }
+        if (w_.empty()) {   // non-NULL pointers for an empty vector
+            w_.reserve(1);
+            v_.reserve(1);
+        }
+    }
+    std::vector<int64_t> detect(int kind, const BowVector &bow, const std::vector<int64_t> *connected, float minScore) {
+        flatten(bow);
+        orbd_query q{};
+        q.kind = kind;
+        q.n = (int32_t)w_.size();
+        q.words = w_.data();
+        q.values = v_.data();
+        q.connected = connected && !connected->empty() ? connected->data() : nullptr;
+        q.n_connected = connected ? (int32_t)connected->size() : 0;
+        q.min_score = minScore;
+        std::vector<int64_t> cand(size() + 1);
+        orbd_result r{};
+        r.cap = (int32_t)cand.size();
+        r.candidates = cand.data();
+        check(orbd_detect(h_, &q, &r), "orbd_detect");
+        cand.resize((size_t)r.n_candidates);
+        return cand;
+    }
+    orbd_db *h_ = nullptr;
+    std::vector<uint32_t> w_;
+    std::vector<double> v_;
+};
+
+// LoopClosing::DetectLoop (LoopClosing.cc:137-285) over a database DB with Scores / DetectLoopCandidates / add
+// (orbslam2_amd::KeyFrameDatabase, or a stand-in). The queue, SetNotErase / SetErase and the map stay with the
+// caller; connected_of(id) is pCandidateKF->GetConnectedKeyFrames() of a candidate.
+template <class DB>
+class LoopClosingT {
+public:
+    typedef std::pair<std::set<int64_t>, int> ConsistentGroup;
+    LoopClosingT(DB *pDB, std::function<std::vector<int64_t>(int64_t)> connected_of)
+        : mpKeyFrameDB(pDB), connected_of_(std::move(connected_of)) {}
+
+    bool DetectLoop(const KeyFrameView &currentKF) {
+        // :152 less than 10 keyframes since the last loop
+        if (currentKF.mnId < mLastLoopKFid + 10) {
+            mpKeyFrameDB->add(currentKF);
+            return false;
+        }
+        // :163-178 the lowest score to a connected keyframe of the covisibility graph
+        const float minScore = mpKeyFrameDB->Scores(currentKF.mBowVec, currentKF.covisibles);
+        mLastMinScore = minScore;
+        // :184
+        const std::vector<int64_t> vpCandidateKFs = mpKeyFrameDB->DetectLoopCandidates(currentKF, minScore);
+        if (vpCandidateKFs.empty()) {   // :188-194
+            mpKeyFrameDB->add(currentKF);
+            mvConsistentGroups.clear();
+            return false;
+        }
+        // :202-268 a candidate's group is consistent with a previous group if they share a keyframe
+        mvpEnoughConsistentCandidates.clear();
+        std::vector<ConsistentGroup> vCurrentConsistentGroups;
+        std::vector<bool> vbConsistentGroup(mvConsistentGroups.size(), false);
+        for (size_t i = 0, iend = vpCandidateKFs.size(); i < iend; i++) {
+            const int64_t pCandidateKF = vpCandidateKFs[i];
+            const std::vector<int64_t> conn = connected_of_(pCandidateKF);
+            std::set<int64_t> spCandidateGroup(conn.begin(), conn.end());
+            spCandidateGroup.insert(pCandidateKF);
+            bool bEnoughConsistent = false;
+            bool bConsistentForSomeGroup = false;
+            for (size_t iG = 0, iendG = mvConsistentGroups.size(); iG < iendG; iG++) {
+                const std::set<int64_t> &sPreviousGroup = mvConsistentGroups[iG].first;
+                bool bConsistent = false;
+                for (std::set<int64_t>::const_iterator sit = spCandidateGroup.begin(), send = spCandidateGroup.end(); sit != send; sit++) {
+                    if (sPreviousGroup.count(*sit)) {
+                        bConsistent = true;
+                        bConsistentForSomeGroup = true;
+                        break;
+                    }
+                }
+                if (bConsistent) {
+                    const int nCurrentConsistency = mvConsistentGroups[iG].second + 1;
+                    if (!vbConsistentGroup[iG]) {
+                        vCurrentConsistentGroups.push_back(std::make_pair(spCandidateGroup, nCurrentConsistency));
+                        vbConsistentGroup[iG] = true;
+                    }
+                    if (nCurrentConsistency >= mnCovisibilityConsistencyTh && !bEnoughConsistent) {
+                        mvpEnoughConsistentCandidates.push_back(pCandidateKF);
+                        bEnoughConsistent = true;
+                    }
+                }
+            }
+            if (!bConsistentForSomeGroup) vCurrentConsistentGroups.push_back(std::make_pair(spCandidateGroup, 0));
+        }
+        mvConsistentGroups = vCurrentConsistentGroups;   // :272
+        mpKeyFrameDB->add(currentKF);                    // :274
+        return !mvpEnoughConsistentCandidates.empty();
+    }
+
+    int64_t mLastLoopKFid = 0;                 // set by the caller's CorrectLoop (LoopClosing.cc:785)
+    int mnCovisibilityConsistencyTh = 3;       // LoopClosing.cc:56
+    std::vector<ConsistentGroup> mvConsistentGroups;
+    std::vector<int64_t> mvpEnoughConsistentCandidates;
+    float mLastMinScore = 1.0f;                // the minScore of the last call that reached the query
+
+private:
+    DB *mpKeyFrameDB;
+    std::function<std::vector<int64_t>(int64_t)> connected_of_;
+};
+using LoopClosing = LoopClosingT<KeyFrameDatabase>;
 
 }  // namespace orbslam2_amd

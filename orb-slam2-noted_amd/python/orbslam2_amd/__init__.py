@@ -173,6 +173,21 @@ SIGNATURES = [
     ("orbo_stage", _I, [_P, _I, _P]),
     ("orbo_run_batch", _I, [_P, _I, _P]),
     ("orbo_fetch", _I, [_P, _I, _P]),
+    ("orbd_create", _I, [_I, _I, C.POINTER(C.c_void_p)]),
+    ("orbd_destroy", None, [_P]),
+    ("orbd_add", _I, [_P, C.c_int64, _P, _P, _I]),
+    ("orbd_add_from_vocab", _I, [_P, C.c_int64, _P, _I]),
+    ("orbd_erase", _I, [_P, C.c_int64]),
+    ("orbd_clear", _I, [_P]),
+    ("orbd_size", _I, [_P, _P]),
+    ("orbd_set_covisibles", _I, [_P, C.c_int64, _P, _I]),
+    ("orbd_detect", _I, [_P, _P, _P]),
+    ("orbd_reserve", _I, [_P, _I]),
+    ("orbd_stage", _I, [_P, _I, _P]),
+    ("orbd_stage_from_vocab", _I, [_P, _I, _P, _P, _I]),
+    ("orbd_run_batch", _I, [_P, _I, _P]),
+    ("orbd_fetch", _I, [_P, _I, _P]),
+    ("orbd_scores", _I, [_P, _P, _P, _I, _P, _I, _P, _P]),
 ]
 
 
@@ -1618,3 +1633,143 @@ class Sim3Optimizer:
             self.stage(s, p)
         self.run_batch(len(probs))
         return [self.fetch(s, len(p["X1c"])) for s, p in enumerate(probs)]
+
+
+# ---- KeyFrameDatabase (orbd_*): DetectLoopCandidates / DetectRelocalizationCandidates ----------
+ORBD_LOOP, ORBD_RELOC = 0, 1
+ORBD_L1_NORM = 0
+ORBD_MAX_WORDS = 4096
+ORBD_MAX_COVISIBLES = 10
+
+
+class OrbdQuery(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("words", C.c_void_p), ("values", C.c_void_p),
+                ("connected", C.c_void_p), ("n_connected", C.c_int32), ("min_score", C.c_float)]
+
+
+class OrbdResult(C.Structure):
+    _fields_ = [("cap", C.c_int32), ("n_candidates", C.c_int32), ("candidates", C.c_void_p), ("n_scored", C.c_int32),
+                ("scored_ids", C.c_void_p), ("scored_si", C.c_void_p), ("scored_words", C.c_void_p),
+                ("acc_score", C.c_void_p), ("acc_best", C.c_void_p), ("max_common_words", C.c_int32),
+                ("min_common_words", C.c_int32)]
+
+
+def orbd_query(q: dict):
+    """(OrbdQuery, arrays it points into) of {"kind", "words", "values"[, "connected", "min_score"]}."""
+    keep = {"words": np.ascontiguousarray(q.get("words", ()), np.uint32),
+            "values": np.ascontiguousarray(q.get("values", ()), np.float64),
+            "connected": np.ascontiguousarray(q.get("connected", ()), np.int64)}
+    Q = OrbdQuery()
+    Q.kind = int(q["kind"])
+    Q.n = len(keep["words"])
+    Q.words, Q.values, Q.connected = (keep[k].ctypes.data for k in ("words", "values", "connected"))
+    Q.n_connected = len(keep["connected"])
+    Q.min_score = float(q.get("min_score", 0.0))
+    return Q, keep
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (include/KeyFrameDatabase.h) resident in HBM: add / erase / clear, and the two
+    queries as scans over every stored BowVector. Queries are dicts {"kind": ORBD_LOOP | ORBD_RELOC,
+    "words", "values", "connected" (ids), "min_score"}; results are dicts of numpy arrays: "candidates"
+    (the reference's return value) plus lScoreAndMatch ("scored_ids", "scored_si", "scored_words") and
+    lAccScoreAndMatch ("acc_score", "acc_best")."""
+
+    def __init__(self, n_words: int, scoring: int = ORBD_L1_NORM):
+        h = C.c_void_p()
+        _check(lib().orbd_create(n_words, scoring, C.byref(h)), "orbd_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orbd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        n = C.c_int32()
+        _check(lib().orbd_size(self._h, C.byref(n)), "orbd_size")
+        return n.value
+
+    def add(self, kf_id: int, words, values):
+        w, v = np.ascontiguousarray(words, np.uint32), np.ascontiguousarray(values, np.float64)
+        _check(lib().orbd_add(self._h, kf_id, _p(w), _p(v), len(w)), "orbd_add")
+
+    def add_from_vocab(self, kf_id: int, voc: "Vocabulary", frame: int):
+        _check(lib().orbd_add_from_vocab(self._h, kf_id, voc._h, frame), "orbd_add_from_vocab")
+
+    def erase(self, kf_id: int):
+        _check(lib().orbd_erase(self._h, kf_id), "orbd_erase")
+
+    def clear(self):
+        _check(lib().orbd_clear(self._h), "orbd_clear")
+
+    def set_covisibles(self, kf_id: int, ids):
+        a = np.ascontiguousarray(ids, np.int64)
+        _check(lib().orbd_set_covisibles(self._h, kf_id, _p(a), len(a)), "orbd_set_covisibles")
+
+    @staticmethod
+    def _result(cap: int):
+        cap = max(cap, 1)
+        out = {"candidates": np.zeros(cap, np.int64), "scored_ids": np.zeros(cap, np.int64),
+               "scored_si": np.zeros(cap, np.float32), "scored_words": np.zeros(cap, np.int32),
+               "acc_score": np.zeros(cap, np.float32), "acc_best": np.zeros(cap, np.int64)}
+        R = OrbdResult()
+        R.cap = cap
+        for k, a in out.items():
+            setattr(R, k, a.ctypes.data)
+        return R, out
+
+    @staticmethod
+    def _unpack(R, out):
+        res = {"candidates": out["candidates"][: R.n_candidates].copy()}
+        for k in ("scored_ids", "scored_si", "scored_words", "acc_score", "acc_best"):
+            res[k] = out[k][: R.n_scored].copy()
+        res["max_common_words"], res["min_common_words"] = R.max_common_words, R.min_common_words
+        return res
+
+    def detect(self, query: dict) -> dict:
+        Q, keep = orbd_query(query)
+        R, out = self._result(len(self))
+        _check(lib().orbd_detect(self._h, C.byref(Q), C.byref(R)), "orbd_detect")
+        return self._unpack(R, out)
+
+    def DetectLoopCandidates(self, words, values, connected, min_score: float) -> np.ndarray:
+        return self.detect({"kind": ORBD_LOOP, "words": words, "values": values, "connected": connected,
+                            "min_score": min_score})["candidates"]
+
+    def DetectRelocalizationCandidates(self, words, values) -> np.ndarray:
+        return self.detect({"kind": ORBD_RELOC, "words": words, "values": values})["candidates"]
+
+    def reserve(self, n_slots: int):
+        _check(lib().orbd_reserve(self._h, n_slots), "orbd_reserve")
+
+    def stage(self, slot: int, query: dict):
+        Q, keep = orbd_query(query)
+        _check(lib().orbd_stage(self._h, slot, C.byref(Q)), "orbd_stage")
+
+    def stage_from_vocab(self, slot: int, query: dict, voc: "Vocabulary", frame: int):
+        Q, keep = orbd_query(query)
+        _check(lib().orbd_stage_from_vocab(self._h, slot, C.byref(Q), voc._h, frame), "orbd_stage_from_vocab")
+
+    def run_batch(self, n_slots: int, stream=None):
+        _check(lib().orbd_run_batch(self._h, n_slots, stream), "orbd_run_batch")
+
+    def fetch(self, slot: int) -> dict:
+        R, out = self._result(len(self))
+        _check(lib().orbd_fetch(self._h, slot, C.byref(R)), "orbd_fetch")
+        return self._unpack(R, out)
+
+    def scores(self, words, values, kf_ids):
+        """(scores[len(kf_ids)], minScore) of LoopClosing::DetectLoop's covisible scan; -1 = not in the database."""
+        w, v = np.ascontiguousarray(words, np.uint32), np.ascontiguousarray(values, np.float64)
+        ids = np.ascontiguousarray(kf_ids, np.int64)
+        sc = np.zeros(max(len(ids), 1), np.float32)
+        mn = C.c_float()
+        _check(lib().orbd_scores(self._h, _p(w), _p(v), len(w), _p(ids), len(ids), _p(sc), C.byref(mn)), "orbd_scores")
+        return sc[: len(ids)], np.float32(mn.value)

@@ -935,3 +935,51 @@ def optimize_sim3_problem(seed: int = 500, n: int = 200, fix_scale: bool = True,
             "q": _quat_xyzw(Rs), "t": ts.astype(np.float64), "s": float(ss), "th2": np.float32(th2),
             "fix_scale": bool(fix_scale), "oct1": oct1.astype(np.int32), "oct2": oct2.astype(np.int32),
             "outlier": outlier, "R12": R12, "t12": t12, "s12": s12}
+
+
+def kfdb_problem(seed: int = 0, n_kf: int = 64, n_words_vocab: int = 1000, words_per_kf=40, n_places: int = 8,
+                 overlap: float = 0.7, n_queries: int = 4, max_covisibles: int = 10):
+    """A KeyFrameDatabase workload: keyframes visit `n_places` places, each place a pool of words; a
+    keyframe draws about `overlap` of its `words_per_kf` words (an int, or a (lo, hi) range) from its
+    place's pool and the rest from the whole vocabulary, so keyframes of a place share many words and
+    others few. BowVectors are L1-normalised positive doubles. Covisibles: up to `max_covisibles` random
+    keyframes of the same place, sometimes an id that is never added (n_kf + 7). Queries alternate
+    relocalisation and loop kinds; a loop query's connected set is a few keyframes of its place.
+    Returns {"n_words", "keyframes": [{"id", "words", "values", "covisibles"}], "queries": [...]}."""
+    rng = np.random.default_rng(seed)
+    pool_size = max(2, min(n_words_vocab, 2 * (words_per_kf if np.isscalar(words_per_kf) else words_per_kf[1])))
+    pools = [rng.choice(n_words_vocab, min(pool_size, n_words_vocab), replace=False) for _ in range(n_places)]
+
+    def vector(place):
+        n = int(words_per_kf) if np.isscalar(words_per_kf) else int(rng.integers(words_per_kf[0], words_per_kf[1] + 1))
+        n = min(n, n_words_vocab)
+        k = min(int(round(overlap * n)), len(pools[place]))
+        w = set(rng.choice(pools[place], k, replace=False).tolist())
+        while len(w) < n:
+            w.update(rng.integers(0, n_words_vocab, n - len(w)).tolist())
+        w = np.array(sorted(w), np.uint32)
+        v = rng.uniform(0.1, 1.0, len(w))
+        return w, (v / v.sum() if len(v) else v).astype(np.float64)
+
+    place = rng.integers(0, n_places, n_kf)
+    kfs = []
+    for i in range(n_kf):
+        w, v = vector(int(place[i]))
+        same = np.nonzero(place == place[i])[0]
+        same = same[same != i]
+        cov = rng.permutation(same)[: int(rng.integers(0, max_covisibles + 1))].tolist()
+        if cov and rng.random() < 0.2:
+            cov[int(rng.integers(0, len(cov)))] = n_kf + 7
+        kfs.append({"id": i, "words": w, "values": v, "covisibles": [int(c) for c in cov], "place": int(place[i])})
+    queries = []
+    for q in range(n_queries):
+        pl = int(rng.integers(0, n_places))
+        w, v = vector(pl)
+        if q % 2 == 0:
+            queries.append({"kind": 1, "words": w, "values": v})
+        else:
+            same = np.nonzero(place == pl)[0]
+            conn = rng.permutation(same)[: min(len(same), 3)].tolist()
+            queries.append({"kind": 0, "words": w, "values": v, "connected": [int(c) for c in conn],
+                            "min_score": float(rng.uniform(0.0, 0.05))})
+    return {"n_words": n_words_vocab, "keyframes": kfs, "queries": queries}
